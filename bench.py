@@ -34,6 +34,17 @@ parity      = the decision log of the LAST timed cycle of each mode, replayed
               (kbgpu.digest), against the oracle's digest of the same seeded
               session committed under tests/golden/digest_c<config>.json (no
               oracle runs here); a mismatch exits non-zero after the line
+--full      = everything beyond the headline figure, each in a run of its own
+              after the timed steps: the full-scan mode (roofline,
+              cycle_roofline_8d, scan_kernel, full_scan_mode), parity, the
+              resident session and the CPU baselines. Without it a run sets
+              up, warms up, times the --steps production cycles and prints
+              the line (metric, value, unit, ms_per_step, p50_cycle_ms, the
+              production mode's own breakdown)
+--dump-outputs DIR = what the last timed cycle returned to its caller, as
+              DIR/decisions.npy (float64 rows task, node, kind, dispatched_at
+              in log order) and, for C5, DIR/evictions.npy (task, by, action);
+              the inputs are seeded, so two builds compare output for output
 --gpus N    = N ranks: under torchrun its WORLD_SIZE must be N; without a
               launcher bench.py starts the N rank processes itself
 N > 1       = ONE cluster with its node axis sharded over the N GPUs (SURVEY §8e,
@@ -347,6 +358,35 @@ def valu_ceiling(pmc, avg_us, rows=None):
     return out
 
 
+DUMP_LIMIT_B = 60 * 10**6  # --dump-outputs writes at most this much array data in all (files under 64 MB)
+
+
+def records_f64(buf, n, fields=4):
+    """The first n records of a ctypes array of int32 x 4 structs (kbg_decision,
+    kbg_eviction) as float64 rows of their first `fields` members."""
+    import numpy as np
+    if n <= 0:
+        return np.zeros((0, fields), dtype=np.float64)
+    return np.frombuffer(buf, dtype=np.int32, count=4 * n).reshape(n, 4)[:, :fields].astype(np.float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: float64 array} as path/<name>.npy. An output
+    larger than its share of DUMP_LIMIT_B is cut to a fixed, seeded sample of
+    its rows (in order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_B // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        row_b = max(1, a.nbytes // max(1, len(a)))
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), size=share // row_b, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+        log(f"bench: wrote {name}.npy {a.shape} to {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -355,9 +395,14 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--candidates", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-faithful", action="store_true", help="skip the 60 s B-faithful CPU baseline")
-    ap.add_argument("--no-resident", action="store_true", help="skip the resident-session (kbg_session_update) lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the full-scan mode "
+                         "(roofline), parity against the golden digest, the resident session, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed cycle's outputs (decision log; C5: evictions too) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-faithful", action="store_true", help="with --full: skip the B-faithful CPU baseline")
+    ap.add_argument("--no-resident", action="store_true", help="with --full: skip the resident-session (kbg_session_update) lines")
     ap.add_argument("--comm", action="store_true",
                     help="open the session through the RCCL sharded entry point even at N=1 (rehearsal)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL) on MI355X; gloo to rehearse on one GPU")
@@ -461,15 +506,17 @@ def main():
         if barrier:
             kdist.barrier()
         agg["stats"] = ssn.stats()
-        # parity of the last timed cycle: its log (still in `buf`, the
-        # session not reset since) replayed through the session's host
-        # objects, then digested with the library's node / job / queue states
-        decs = decision_list(buf, nout.value)
-        agg["log_sha256"] = log_sha(decs)
-        binder = FakeBinder()
-        cache.binder = binder
-        replay(ssn, decs, "allocate")
-        agg["digest"] = digest_outputs(session_output(ssn, binder.binds))
+        agg["last_decisions"] = records_f64(buf, nout.value)  # what the last timed cycle returned
+        if args.full:
+            # parity of the last timed cycle: its log (still in `buf`, the
+            # session not reset since) replayed through the session's host
+            # objects, then digested with the library's node / job / queue states
+            decs = decision_list(buf, nout.value)
+            agg["log_sha256"] = log_sha(decs)
+            binder = FakeBinder()
+            cache.binder = binder
+            replay(ssn, decs, "allocate")
+            agg["digest"] = digest_outputs(session_output(ssn, binder.binds))
         agg["n_nodes"] = len(ssn.nodes)
         agg["words"] = (((agg["n_nodes"] + 63) // 64) + world - 1) // world  # 64-node words a rank's launch walks
         agg["pending"] = ssn.flat.pending_count
@@ -617,7 +664,10 @@ def main():
         contended_bench(args, fx, cache, base_opts, comm, rank, world, cid, open_ms_first)
         return
     prod = run_mode(0, args.steps, args.warmup, True)      # production: grouped shapes
-    full = run_mode(1, max(1, min(10, args.steps)), 2, False)  # SURVEY roofline rule: every task scans all N
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"decisions": prod["last_decisions"]})
+    # --full, SURVEY roofline rule: every task scans all N
+    full = run_mode(1, max(1, min(10, args.steps)), 2, False) if args.full else None
     decisions = prod["decisions"]
     elapsed, total_decisions = kdist.aggregate(prod["elapsed"], decisions, sharded=world > 1)
     tp = "RCCL" if comm is None or comm.transport == "rccl" else "host shared-memory"
@@ -659,16 +709,9 @@ def main():
                                   if world > 1 else "single-gpu",
                    "batch_tasks": base_opts.get("batch_tasks", 8192),
                    "candidates": base_opts.get("candidates", 32)},
-        "roofline": kernel_roofline(full, "full_scan"),
-        "roofline_note": "full-scan mode (every task evaluation scans all N nodes on the device, SURVEY 8(d) cursor "
-                         "rule); bound = VALU issue (PMC), HBM traffic and the 8(d) byte figure beside it; `value` "
-                         "is the production mode, which groups identical (class, request) shapes",
+        "full": args.full,
         "rccl_ranks": rccl_ranks,
         "comm_transport": comm.transport if comm is not None else None,
-        "cycle_roofline_8d": cycle_roofline(full, "full_scan"),
-        "scan_kernel": scan_kernel(full, "full_scan"),
-        "full_scan_mode": {"placements_per_s": full["decisions"] / full["elapsed"],
-                           "p50_cycle_ms": statistics.median(full["cycle_ms"]), "breakdown": breakdown(full)},
         "production_mode": {"equivalent_8d": {("equiv_frac" if k == "frac" else k): v
                                               for k, v in cycle_roofline(prod, "grouped").items()
                                               if k not in ("bound", "peak", "unit")},
@@ -678,12 +721,23 @@ def main():
         "decisions_per_cycle": decisions // max(1, args.steps),
         "open_ms": st.open_ms,
         "open_ms_first_in_process": open_ms_first,
-        "parity": dict(parity_verdict(cid, {"production": prod["digest"], "full_scan": full["digest"]}),
-                       log_sha256={"production": prod["log_sha256"], "full_scan": full["log_sha256"]}),
     }
-    if world == 1 and not args.no_resident:
+    if args.full:
+        line.update({
+            "roofline": kernel_roofline(full, "full_scan"),
+            "roofline_note": "full-scan mode (every task evaluation scans all N nodes on the device, SURVEY 8(d) "
+                             "cursor rule); bound = VALU issue (PMC), HBM traffic and the 8(d) byte figure beside it; "
+                             "`value` is the production mode, which groups identical (class, request) shapes",
+            "cycle_roofline_8d": cycle_roofline(full, "full_scan"),
+            "scan_kernel": scan_kernel(full, "full_scan"),
+            "full_scan_mode": {"placements_per_s": full["decisions"] / full["elapsed"],
+                               "p50_cycle_ms": statistics.median(full["cycle_ms"]), "breakdown": breakdown(full)},
+            "parity": dict(parity_verdict(cid, {"production": prod["digest"], "full_scan": full["digest"]}),
+                           log_sha256={"production": prod["log_sha256"], "full_scan": full["log_sha256"]}),
+        })
+    if args.full and world == 1 and not args.no_resident:
         line["resident_session"] = resident_bench(cache, fx, base_opts)
-    if world == 1 and not args.no_cpu_baseline:  # the CPU baseline is an N=1 figure
+    if args.full and world == 1 and not args.no_cpu_baseline:  # the CPU baseline is an N=1 figure
         # bounded samples where a full cycle takes longer than ~30 s of CPU
         # (C3's failing tasks walk every node, C4 is 500k tasks)
         budget = {1: 0.0, 2: 0.0, 3: 20.0}.get(cid, 60.0)
@@ -706,7 +760,7 @@ def main():
     if comm is not None:
         comm.close()
     kdist.shutdown()
-    if line["parity"]["ok"] is False:
+    if args.full and line["parity"]["ok"] is False:
         log(f"bench: PARITY MISMATCH against {line['parity']['golden']}: {line['parity']}")
         sys.exit(3)
 
@@ -886,14 +940,20 @@ def contended_bench(args, fx, cache, base_opts, comm, rank, world, cid, open_ms_
     # session through the framework's actions (the same entry points, each
     # action's decisions and evictions replayed through the session) whose
     # log must be the timed one and whose digest must be the oracle's
-    timed_sha = log_sha(decision_list(buf, nout.value), evictions_list(ssn))
-    binder = FakeBinder()
-    cache.binder = binder
-    _abi.check(L.kbg_session_reset(ssn.handle))
-    for name in fx["actions"]:
-        get_action(name).execute(ssn)
-    verify_sha = log_sha(ssn.decisions, evictions_list(ssn))
-    digest = digest_outputs(session_output(ssn, binder.binds))
+    timed_evictions = evictions_list(ssn)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(args.dump_outputs, {"decisions": records_f64(buf, nout.value),
+                                         "evictions": np.array(timed_evictions, dtype=np.float64).reshape(-1, 3)})
+    if args.full:
+        timed_sha = log_sha(decision_list(buf, nout.value), timed_evictions)
+        binder = FakeBinder()
+        cache.binder = binder
+        _abi.check(L.kbg_session_reset(ssn.handle))
+        for name in fx["actions"]:
+            get_action(name).execute(ssn)
+        verify_sha = log_sha(ssn.decisions, evictions_list(ssn))
+        digest = digest_outputs(session_output(ssn, binder.binds))
     ssn.close()
     elapsed, total = kdist.aggregate(elapsed_local, dec, sharded=world > 1)
     nodes_per_rank = n_nodes / max(1, world)
@@ -947,24 +1007,27 @@ def contended_bench(args, fx, cache, base_opts, comm, rank, world, cid, open_ms_
         "phase_ms_p50": {k: statistics.median(v) for k, v in phase.items()},
         "open_ms": st.open_ms,
         "open_ms_first_in_process": open_ms_first,
+        "full": args.full,
     }
-    par = parity_verdict(cid, {"cycle": digest})
-    par["timed_cycle_log_sha256"] = timed_sha
-    par["verify_cycle_log_equal"] = verify_sha == timed_sha
-    par["checked"] = ("the last timed cycle's raw log (decisions and evictions) equals that of one more cycle on the "
-                      "reset session through the framework's actions, whose outputs (" + par["checked"] + ") match "
-                      "the golden digest")
-    if not par["verify_cycle_log_equal"]:
-        par["ok"] = False
-    line["parity"] = par
-    if world == 1 and not args.no_cpu_baseline:
+    par = None
+    if args.full:
+        par = parity_verdict(cid, {"cycle": digest})
+        par["timed_cycle_log_sha256"] = timed_sha
+        par["verify_cycle_log_equal"] = verify_sha == timed_sha
+        par["checked"] = ("the last timed cycle's raw log (decisions and evictions) equals that of one more cycle on "
+                          "the reset session through the framework's actions, whose outputs (" + par["checked"] +
+                          ") match the golden digest")
+        if not par["verify_cycle_log_equal"]:
+            par["ok"] = False
+        line["parity"] = par
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(fx, f"C{cid} ({', '.join(fx['actions'])})")
     if rank == 0:
         emit(line)
     if comm is not None:
         comm.close()
     kdist.shutdown()
-    if par["ok"] is False:
+    if par is not None and par["ok"] is False:
         log(f"bench: PARITY MISMATCH: {par}")
         sys.exit(3)
 

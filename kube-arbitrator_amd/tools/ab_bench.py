@@ -12,7 +12,7 @@ steps = os.environ.get("STEPS", "10")
 for rep in range(int(os.environ.get("REPS", "3"))):
     for v in sys.argv[1:]:
         code = ("import sys; sys.path.insert(0,'kube-arbitrator_amd'); from kbgpu import _abi; _abi.LIB_PATH='%s'; "
-                "sys.argv=['bench.py','--config','%s','--steps','%s','--warmup','2','--no-cpu-baseline'%s]; "
+                "sys.argv=['bench.py','--full','--config','%s','--steps','%s','--warmup','2','--no-cpu-baseline'%s]; "
                 "import runpy; runpy.run_path('bench.py', run_name='__main__')") % (v, cfg, steps, "" if resident else ",'--no-resident'")
         env = dict(os.environ)
         for kv in v.split("@")[1:]:  # lib.so@KEY=VAL@...: the variant's environment

@@ -19,7 +19,7 @@ def main():
             for kv in filter(None, spec.split(",")):
                 k, v = kv.split("=", 1)
                 env[k] = v
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cid, "--steps", "10",
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", cid, "--steps", "10",
                                   "--warmup", "2", "--no-cpu-baseline", "--no-resident"],
                                  capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
             d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -59,7 +59,7 @@ def main():
     out["source"] = (f"{', '.join(srcs[c] for c in sorted(srcs))} (profiles/summarize_pmc.py over scripts/gpurun/pmc.sh): rocprofv3 "
                      "--kernel-trace --stats, then separate --pmc passes (FETCH_SIZE / WRITE_SIZE / "
                      "TCC_HIT_sum+TCC_MISS_sum / SQ_INSTS_VALU,SQ_WAVES,... / SQ_WAIT_ANY,...) of `python3 bench.py "
-                     "--config {3,5} --steps 3 --warmup 1 --no-cpu-baseline --no-resident`; read = 2 x FETCH_SIZE "
+                     "--full --config {3,5} --steps 3 --warmup 1 --no-cpu-baseline --no-resident`; read = 2 x FETCH_SIZE "
                      "(gfx950 correction, MI355X_MICROARCH.md HBM section); FETCH/WRITE count Infinity-Cache hits too")
     if c4:
         out["by_nodes"] = {"20000": dict(scan_modes(c4), source=f"{srcs[4]} (scripts/gpurun/pmc.sh CFGS=4, same "

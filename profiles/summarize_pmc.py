@@ -59,7 +59,7 @@ def rows(path):
 def main():
     d, cfg = sys.argv[1], sys.argv[2]
     out = {"source": f"scripts/gpurun/pmc.sh: rocprofv3 --kernel-trace --stats, then one --pmc pass per counter group, of "
-                     f"`python3 bench.py --config {cfg} --steps 3 --warmup 1 --no-cpu-baseline --no-resident`",
+                     f"`python3 bench.py --full --config {cfg} --steps 3 --warmup 1 --no-cpu-baseline --no-resident`",
            "config": int(cfg), "kernels": {}}
     ks = out["kernels"]
     for r in rows(os.path.join(d, f"c{cfg}_kt", "kt_kernel_trace.csv")):

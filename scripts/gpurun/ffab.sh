@@ -18,7 +18,7 @@ if [ -n "$TESTS" ]; then
   tail -3 $O/pytest.log
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-resident > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-resident > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench.json'));print('bench', d['value'], d['p50_cycle_ms'], d['roofline']['frac'], d['roofline']['avg_launch_us'], d['parity']['ok'])"
 fi
 echo FFAB_DONE

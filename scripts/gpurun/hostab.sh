@@ -14,7 +14,7 @@ fi
 for i in 1 2 3; do
   for v in ${A:-1} ${B:-0}; do
     if [ "$v" = "-" ]; then SETV="-u $VAR"; else SETV="$VAR=$v"; fi
-    env $SETV timeout -k 10 300 python bench.py --config ${CFG:-3} --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${EXTRA} > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -30 $O/b_${v}_$i.err; exit 1; }
+    env $SETV timeout -k 10 300 python bench.py --full --config ${CFG:-3} --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${EXTRA} > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -30 $O/b_${v}_$i.err; exit 1; }
     python -c "
 import json,sys; d=json.load(open('$O/b_${v}_$i.json')); b=d['production_mode']['breakdown']; r=d.get('resident_session') or {}
 print('$VAR=$v', round(d['value']/1e6,2), 'p50', round(d['p50_cycle_ms'],3), 'eng', round(b['host_engine_ms'],2), 'res', round(b['host_resolve_ms'],2), 'rk', b['resolve_rechecks'], 'ov', b['overlapped_batches'], 'dev', round(b['device_roundtrip_ms'],2), 'churn', r.get('churn_allocate_ms_p50'), 'parity', d['parity']['ok'])"

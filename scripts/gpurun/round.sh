@@ -17,11 +17,11 @@ if [ -z "$NO_SMOKE" ]; then
   tail -2 $O/smoke.log
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 600 python bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; cat $O/bench.json; exit 1; }
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; cat $O/bench.json; exit 1; }
   cat $O/bench.json
 fi
 for cfg in $CFGS; do
-  timeout -k 10 600 python bench.py --config $cfg ${CFG_ARGS:---steps 10 --warmup 2 --no-cpu-baseline} > $O/bench_c$cfg.json 2> $O/bench_c$cfg.err || { tail -30 $O/bench_c$cfg.err; cat $O/bench_c$cfg.json; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $cfg ${CFG_ARGS:---steps 10 --warmup 2 --no-cpu-baseline} > $O/bench_c$cfg.json 2> $O/bench_c$cfg.err || { tail -30 $O/bench_c$cfg.err; cat $O/bench_c$cfg.json; exit 1; }
   cat $O/bench_c$cfg.json
 done
 if [ -n "$PMC" ]; then

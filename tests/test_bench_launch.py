@@ -62,3 +62,44 @@ def test_parity_verdict_against_golden_digest():
     v = bench.parity_verdict(1, {"production": dg, "full_scan": bad})
     assert v["ok"] is False and v["full_scan"] == {"mismatch": ["binds"]}
     assert bench.parity_verdict(99, {"production": dg})["ok"] is None  # no golden digest for the config
+
+
+def _bench_mod():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_float64_records(tmp_path):
+    """--dump-outputs' writer: ctypes decision records become float64 rows in
+    log order, one <name>.npy each."""
+    import numpy as np
+    bench = _bench_mod()
+    sys.path.insert(0, os.path.join(ROOT, "kube-arbitrator_amd"))
+    from kbgpu import _abi
+    buf = (_abi.kbg_decision * 5)()
+    for i in range(5):
+        buf[i].task, buf[i].node, buf[i].kind, buf[i].dispatched_at = 10 + i, 2 * i, i % 2, -1 if i == 4 else i
+    rows = bench.records_f64(buf, 4)
+    assert rows.dtype == np.float64 and rows.tolist() == [[10 + i, 2 * i, i % 2, i] for i in range(4)]
+    assert bench.records_f64(buf, 0).shape == (0, 4)
+    bench.dump_outputs(str(tmp_path / "o"), {"decisions": rows, "evictions": np.zeros((0, 3))})
+    assert sorted(os.listdir(tmp_path / "o")) == ["decisions.npy", "evictions.npy"]
+    assert np.array_equal(np.load(tmp_path / "o" / "decisions.npy"), rows)
+
+
+def test_dump_outputs_samples_what_exceeds_the_limit(tmp_path, monkeypatch):
+    """An output above the size limit is cut to a fixed, seeded sample of its
+    rows, in order, the same on every call."""
+    import numpy as np
+    bench = _bench_mod()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_B", 64 * 32)  # 64 rows of 4 float64
+    big = np.arange(4000, dtype=np.float64).reshape(1000, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"decisions": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"decisions": big})
+    a = np.load(tmp_path / "a" / "decisions.npy")
+    assert a.shape == (64, 4) and a.nbytes <= 64 * 32
+    assert np.array_equal(a, np.load(tmp_path / "b" / "decisions.npy"))
+    assert np.all(np.diff(a[:, 0]) > 0) and np.all(a[:, 1] == a[:, 0] + 1)
