@@ -1,0 +1,376 @@
+// Developer tool (not part of libkbgpu.so): kernel probes. Each entry point
+// takes host arrays, allocates what it needs, runs one launcher of
+// kbg_device.hpp (or a short chain of them) on a stream of its own,
+// synchronises, copies the outputs back and frees everything. There is no
+// session and no Grouper: tests/test_kernels_gpu.py builds the inputs and
+// compares the raw device output with a plain reference (tests/kernel_ref.py).
+//
+// Output buffers are filled with kProbeSentinel bytes before the launch and
+// are followed by a guard region of kProbeGuardBytes of the same pattern; the
+// whole buffers, guards included, are returned, so a store outside the
+// documented range shows. The probes exist to test legal launches: anything
+// the session code would never produce is rejected on the host (-2) without
+// a launch. Return 0, or a negative code with kbg_tool_probe_error() set.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../csrc/kbg_device.hpp"
+
+namespace {
+
+constexpr int32_t kProbeGuardBytes = 4096;
+constexpr int kProbeSentinel = 0xA5;
+constexpr int32_t kProbeInvalid = -2, kProbeHip = -3;
+
+thread_local std::string t_error;
+
+int32_t reject(const char* what) {
+  t_error = what;
+  return kProbeInvalid;
+}
+
+// Every allocation of one probe call, freed when it returns.
+struct Scope {
+  std::vector<void*> dev, host;
+  hipStream_t stream = nullptr;
+  ~Scope() {
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : host) (void)hipHostFree(p);
+  }
+};
+
+int32_t hip_fail(hipError_t e, const char* what) {
+  t_error = std::string(what) + ": " + hipGetErrorString(e);
+  return kProbeHip;
+}
+
+#define PROBE_TRY(expr)                                  \
+  do {                                                   \
+    const hipError_t e_ = (expr);                        \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr);    \
+  } while (0)
+
+// Device memory holding a copy of `src` (or `fill` bytes when src is null).
+template <class T>
+hipError_t dev_copy(Scope& sc, T** out, const T* src, size_t count, int fill = 0) {
+  void* p = nullptr;
+  const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return e;
+  sc.dev.push_back(p);
+  e = src ? hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipMemset(p, fill, bytes);
+  *out = (T*)p;
+  return e;
+}
+
+// Host-mapped (zero-copy, coherent) memory as the session's staging uses;
+// `dev` is its device address.
+template <class T>
+hipError_t mapped(Scope& sc, T** host, T** dev, size_t bytes) {
+  void* h = nullptr;
+  hipError_t e = hipHostMalloc(&h, std::max<size_t>(bytes, 16), hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return e;
+  sc.host.push_back(h);
+  void* d = nullptr;
+  e = hipHostGetDevicePointer(&d, h, 0);
+  *host = (T*)h;
+  *dev = (T*)d;
+  return e;
+}
+
+bool table_ok(int32_t stride, int32_t tab_lo, int32_t tab_n) {
+  return stride >= 1 && tab_lo >= 0 && tab_n >= 1 && tab_n <= stride;
+}
+
+bool classes_ok(const kbg::TaskRec* t, int32_t n, int32_t classes) {
+  for (int32_t i = 0; i < n; ++i)
+    if (t[i].cls < 0 || t[i].cls >= classes) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" const char* kbg_tool_probe_error() { return t_error.c_str(); }
+extern "C" int32_t kbg_tool_probe_guard_bytes() { return kProbeGuardBytes; }
+extern "C" int32_t kbg_tool_probe_sentinel() { return kProbeSentinel; }
+
+// The scalar fields of FirstFitArgs as given, then the probe's own.
+struct kbg_probe_ff {
+  int32_t G, n_shapes, mw, n_nodes, W, w_lo, w_hi, tab_lo, tab_n, cap_check, early_exit, complete, splits, split_words,
+      rows, info_stride, part0, mask_w0, runs;
+  int32_t stride;    // rows of the node table block
+  int32_t classes;   // rows of class_mask
+  int32_t int_mode;
+};
+
+// kbg_firstfit_kernel. nodes: the table block (FirstFitArgs.nodes layout,
+// stride * 56 bytes); class_mask [classes][W]; shapes [n_shapes]; row_shape
+// [G] or null; run_end [n_shapes] (runs != 0) or null. info_out: n_shapes *
+// info_stride words + guard; masks_out: n_shapes * mw pairs + guard.
+extern "C" int32_t kbg_tool_probe_firstfit(const kbg_probe_ff* p, const void* nodes, const uint64_t* class_mask,
+                                           const kbg::TaskRec* shapes, const uint32_t* row_shape,
+                                           const uint16_t* run_end, void* info_out, void* masks_out) {
+  t_error.clear();
+  if (!p || !nodes || !class_mask || !shapes || !info_out || !masks_out) return reject("null argument");
+  if (p->G < 1 || p->n_shapes < 1 || p->classes < 1) return reject("empty launch");
+  const kbg::FfGeometry geo = kbg::firstfit_geometry(p->G, !p->early_exit);
+  if (p->rows < 1 || p->rows > geo.variant) return reject("rows outside 1..geometry.variant");
+  if (p->W < 1 || p->w_lo < 0 || p->w_lo >= p->w_hi || p->w_hi > p->W) return reject("w_lo / w_hi outside W");
+  const int32_t tw = p->w_hi - p->w_lo;
+  if (p->complete && tw > kbg::kFfRoundWords) return reject("complete with more than kFfRoundWords words");
+  if (p->n_nodes < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (!table_ok(p->stride, p->tab_lo, p->tab_n)) return reject("window rows outside the table block");
+  if (p->mask_w0 < 0 || p->mask_w0 > p->w_lo || p->mw < p->w_hi - p->mask_w0) return reject("mw too small");
+  if (p->splits < 1 || p->splits > kbg::kFfMaxSplits || p->split_words < 1 ||
+      (int64_t)p->splits * p->split_words < tw)
+    return reject("splits * split_words < w_hi - w_lo");
+  if ((int64_t)(p->splits - 1) * p->split_words >= tw) return reject("an empty part");
+  if (p->part0 < 0 || p->info_stride < p->part0 + p->splits) return reject("info_stride too small");
+  if (!classes_ok(shapes, p->n_shapes, p->classes)) return reject("shape class outside class_mask");
+  if (p->runs) {
+    if (!run_end || row_shape || p->n_shapes > kbg::kInlineShapes) return reject("runs need inline shapes and run_end");
+    uint32_t prev = 0;
+    for (int32_t s = 0; s < p->n_shapes; ++s) {
+      if (run_end[s] <= prev) return reject("run_end not increasing");
+      prev = run_end[s];
+    }
+    if ((int32_t)prev != p->G) return reject("run_end does not add up to G");
+  } else if (row_shape) {
+    std::vector<int> writers(p->n_shapes, 0);
+    for (int32_t g = 0; g < p->G; ++g) {
+      const uint32_t s = row_shape[g] & ~kbg::kRowWriter;
+      if (s >= (uint32_t)p->n_shapes) return reject("row_shape outside the shape table");
+      if (row_shape[g] & kbg::kRowWriter) writers[s]++;
+    }
+    for (int w : writers)
+      if (w > 1) return reject("two writer rows of one shape");
+  } else if (p->G > p->n_shapes) {
+    return reject("G > n_shapes without a row map");
+  }
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  kbg::FirstFitArgs a{};
+  double* d_nodes = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d_nodes, (const char*)nodes, (size_t)p->stride * 56));
+  uint64_t* d_cm = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_cm, class_mask, (size_t)p->classes * p->W));
+  a.nodes = d_nodes;
+  a.class_mask = d_cm;
+  if (p->n_shapes <= kbg::kInlineShapes) {
+    std::copy(shapes, shapes + p->n_shapes, a.inl);
+  } else {  // host-mapped, as device_launch does
+    kbg::TaskRec *h = nullptr, *d = nullptr;
+    PROBE_TRY(mapped(sc, &h, &d, (size_t)p->n_shapes * sizeof(kbg::TaskRec)));
+    std::copy(shapes, shapes + p->n_shapes, h);
+    a.shapes = d;
+  }
+  if (p->runs) {
+    std::copy(run_end, run_end + p->n_shapes, a.run_end);
+  } else if (row_shape) {
+    uint32_t *h = nullptr, *d = nullptr;
+    PROBE_TRY(mapped(sc, &h, &d, (size_t)p->G * 4));
+    std::copy(row_shape, row_shape + p->G, h);
+    a.row_shape = d;
+  }
+  const size_t info_bytes = (size_t)p->n_shapes * p->info_stride * 4 + kProbeGuardBytes;
+  const size_t mask_bytes = (size_t)p->n_shapes * p->mw * sizeof(kbg::MaskPair) + kProbeGuardBytes;
+  char *h_info = nullptr, *h_masks = nullptr;
+  PROBE_TRY(mapped(sc, &h_info, (char**)&a.info, info_bytes));
+  PROBE_TRY(mapped(sc, &h_masks, (char**)&a.masks, mask_bytes));
+  memset(h_info, kProbeSentinel, info_bytes);
+  memset(h_masks, kProbeSentinel, mask_bytes);
+  a.avail = nullptr;
+  a.stride = p->stride;
+  a.G = p->G;
+  a.n_shapes = p->n_shapes;
+  a.mw = p->mw;
+  a.n_nodes = p->n_nodes;
+  a.W = p->W;
+  a.w_lo = p->w_lo;
+  a.w_hi = p->w_hi;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  a.cap_check = p->cap_check;
+  a.early_exit = p->early_exit;
+  a.complete = p->complete;
+  a.splits = p->splits;
+  a.split_words = p->split_words;
+  a.rows = p->rows;
+  a.info_stride = p->info_stride;
+  a.part0 = p->part0;
+  a.mask_w0 = p->mask_w0;
+  a.runs = p->runs;
+  PROBE_TRY(kbg::launch_firstfit(a, p->int_mode ? 1 : 0, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  memcpy(info_out, h_info, info_bytes);
+  memcpy(masks_out, h_masks, mask_bytes);
+  return 0;
+}
+
+struct kbg_probe_scan {
+  int32_t n_nodes, W, Wl, slots, tab_lo, stride, classes, n_tasks, cap_check, int_mode, w_lo, w_hi;
+};
+
+// kbg_scan_kernel, one launch per slot as a rank of a sharded session scans
+// its own, into one [slot][plane][quad][row][4] buffer, then
+// kbg_select_kernel over [w_lo, w_hi). tasks [n_tasks] (padded here as
+// kbg_pad_rows asks); cap_off [n_tasks + 1]. bits_out: slots * 2 * n_tasks *
+// kbg_slot_words(Wl) words + guard; cand_out: cap_off[n_tasks] words + guard;
+// count_out: n_tasks words + guard.
+extern "C" int32_t kbg_tool_probe_scan_select(const kbg_probe_scan* p, const void* nodes, const uint64_t* class_mask,
+                                              const kbg::TaskRec* tasks, const uint32_t* cap_off, void* bits_out,
+                                              void* cand_out, void* count_out) {
+  t_error.clear();
+  if (!p || !nodes || !class_mask || !tasks || !cap_off || !bits_out || !cand_out || !count_out)
+    return reject("null argument");
+  if (p->n_tasks < 1 || p->classes < 1 || p->Wl < 1 || p->slots < 1) return reject("empty launch");
+  if (p->W < 1 || p->n_nodes < 1 || p->n_nodes > p->W * 64 || (int64_t)p->slots * p->Wl < p->W)
+    return reject("slots do not cover W");
+  if ((int64_t)(p->slots - 1) * p->Wl >= p->W) return reject("a slot past W");
+  if (p->w_lo < 0 || p->w_lo > p->w_hi || p->w_hi > p->W) return reject("w_lo / w_hi outside W");
+  // the scan kernel reads the row of every node below n_nodes
+  if (p->stride < 1 || p->tab_lo != 0 || p->n_nodes > p->stride) return reject("nodes outside the table block");
+  if (!classes_ok(tasks, p->n_tasks, p->classes)) return reject("task class outside class_mask");
+  for (int32_t t = 0; t < p->n_tasks; ++t)
+    if (cap_off[t + 1] < cap_off[t]) return reject("cap_off not increasing");
+  if (cap_off[0] != 0) return reject("cap_off[0] != 0");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  double* d = nullptr;
+  const size_t L = (size_t)p->stride;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  const kbg::NodeSoA soa{d, d + L, d + 2 * L, d + 3 * L, d + 4 * L, d + 5 * L, (int32_t*)(d + 6 * L),
+                         (int32_t*)(d + 6 * L) + L};
+  uint64_t* d_cm = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_cm, class_mask, (size_t)p->classes * p->W));
+  std::vector<kbg::TaskRec> rows(tasks, tasks + p->n_tasks);
+  rows.resize(kbg::kbg_pad_rows(p->n_tasks), tasks[0]);  // padding rows: scanned, never stored
+  kbg::TaskRec* d_tasks = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_tasks, rows.data(), rows.size()));
+  uint32_t* d_capoff = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_capoff, cap_off, (size_t)p->n_tasks + 1));
+  const size_t slot_words = (size_t)2 * p->n_tasks * kbg::kbg_slot_words(p->Wl);
+  const size_t bits_bytes = (size_t)p->slots * slot_words * 8 + kProbeGuardBytes;
+  const size_t cand_bytes = (size_t)cap_off[p->n_tasks] * 4 + kProbeGuardBytes;
+  const size_t count_bytes = (size_t)p->n_tasks * 4 + kProbeGuardBytes;
+  char *d_bits = nullptr, *d_cand = nullptr, *d_count = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_bits, (const char*)nullptr, bits_bytes, kProbeSentinel));
+  PROBE_TRY(dev_copy(sc, &d_cand, (const char*)nullptr, cand_bytes, kProbeSentinel));
+  PROBE_TRY(dev_copy(sc, &d_count, (const char*)nullptr, count_bytes, kProbeSentinel));
+  for (int32_t s = 0; s < p->slots; ++s) {
+    const kbg::ScanGeom geo{p->n_nodes, p->W, p->Wl, s * p->Wl, p->Wl, p->tab_lo};
+    PROBE_TRY(kbg::launch_scan(soa, geo, d_cm, d_tasks, p->n_tasks, p->cap_check, p->int_mode ? 1 : 0,
+                               (uint64_t*)d_bits + (size_t)s * slot_words, sc.stream));
+  }
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(bits_out, d_bits, bits_bytes, hipMemcpyDeviceToHost));
+  // The select kernel reads only the words [w_lo, w_hi) <= W the scans wrote.
+  PROBE_TRY(kbg::launch_select((const uint64_t*)d_bits, p->w_lo, p->w_hi, p->Wl, p->n_tasks, d_capoff,
+                               (uint32_t*)d_cand, (uint32_t*)d_count, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(cand_out, d_cand, cand_bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(count_out, d_count, count_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+struct kbg_probe_fit {
+  int32_t n_nodes, W, stride, classes, tab_lo, tab_n, nq, cap_check, n_dec;
+};
+
+// kbg_fitdelta_kernel. hoff [n_nodes + 1] (global nodes); hk, na [n_dec];
+// hold [n_dec][3]; q [nq]. out: nq * 4 words + guard (host-mapped).
+extern "C" int32_t kbg_tool_probe_fitdelta(const kbg_probe_fit* p, const void* nodes, const uint64_t* class_mask,
+                                           const int32_t* hoff, const int32_t* hk, const double* hold,
+                                           const int32_t* na, const kbg::FitQuery* q, void* out) {
+  t_error.clear();
+  if (!p || !nodes || !class_mask || !hoff || !hk || !hold || !na || !q || !out) return reject("null argument");
+  if (p->nq < 1 || p->classes < 1) return reject("empty launch");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (!table_ok(p->stride, p->tab_lo, p->tab_n) || p->tab_lo + p->tab_n > p->n_nodes)
+    return reject("window rows outside the table block");
+  if (hoff[0] != 0 || hoff[p->n_nodes] != p->n_dec) return reject("hoff does not span the decisions");
+  for (int32_t n = 0; n < p->n_nodes; ++n)
+    if (hoff[n + 1] < hoff[n]) return reject("hoff not increasing");
+  for (int32_t i = 0; i < p->n_dec; ++i)
+    if (na[i] < -1 || na[i] >= p->n_dec) return reject("na outside the decisions");
+  for (int32_t i = 0; i < p->nq; ++i)
+    if (q[i].cls < 0 || q[i].cls >= p->classes || q[i].end < 0) return reject("query outside class_mask");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  kbg::FitArgs a{};
+  PROBE_TRY(dev_copy(sc, (char**)&a.nodes, (const char*)nodes, (size_t)p->stride * 56));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&a.class_mask, class_mask, (size_t)p->classes * p->W));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.hoff, hoff, (size_t)p->n_nodes + 1));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.hk, hk, (size_t)p->n_dec));
+  PROBE_TRY(dev_copy(sc, (double**)&a.hold, hold, (size_t)p->n_dec * 3));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.na, na, (size_t)p->n_dec));
+  PROBE_TRY(dev_copy(sc, (kbg::FitQuery**)&a.q, q, (size_t)p->nq));
+  a.stride = p->stride;
+  a.W = p->W;
+  a.nq = p->nq;
+  a.cap_check = p->cap_check;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  const size_t out_bytes = (size_t)p->nq * 16 + kProbeGuardBytes;
+  char* h_out = nullptr;
+  PROBE_TRY(mapped(sc, &h_out, (char**)&a.out, out_bytes));
+  memset(h_out, kProbeSentinel, out_bytes);
+  PROBE_TRY(kbg::launch_fitdelta(a, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  memcpy(out, h_out, out_bytes);
+  return 0;
+}
+
+// kbg_apply_kernel on the table, kbg_mask_apply_kernel on the mask words,
+// then kbg_copy16_kernel of the table into a second buffer. `nodes`
+// (stride * 56 bytes, stride even: whole 16-byte units) and `mask`
+// [mask_words] are updated in place; copy_out: stride * 56 bytes + guard.
+extern "C" int32_t kbg_tool_probe_apply(int32_t stride, void* nodes, const kbg::NodeDelta* deltas, int32_t n_deltas,
+                                        uint64_t* mask, int32_t mask_words, const kbg::MaskDelta* mdeltas,
+                                        int32_t n_mdeltas, void* copy_out) {
+  t_error.clear();
+  if (!nodes || !deltas || !mask || !mdeltas || !copy_out) return reject("null argument");
+  if (stride < 2 || (stride & 1) || mask_words < 1 || n_deltas < 1 || n_mdeltas < 1) return reject("empty launch");
+  for (int32_t i = 0; i < n_deltas; ++i)
+    if (deltas[i].node < 0 || deltas[i].node >= stride) return reject("delta outside the table");
+  for (int32_t i = 0; i < n_mdeltas; ++i)
+    if (mdeltas[i].index >= (uint32_t)mask_words) return reject("mask delta outside the mask");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)stride, bytes = L * 56;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, bytes));
+  const kbg::NodeSoA soa{d, d + L, d + 2 * L, d + 3 * L, d + 4 * L, d + 5 * L, (int32_t*)(d + 6 * L),
+                         (int32_t*)(d + 6 * L) + L};
+  uint64_t* d_mask = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_mask, mask, (size_t)mask_words));
+  // deltas are read in place from host-mapped memory, as the session's are
+  kbg::NodeDelta *h_nd = nullptr, *d_nd = nullptr;
+  PROBE_TRY(mapped(sc, &h_nd, &d_nd, (size_t)n_deltas * sizeof(kbg::NodeDelta)));
+  std::copy(deltas, deltas + n_deltas, h_nd);
+  kbg::MaskDelta *h_md = nullptr, *d_md = nullptr;
+  PROBE_TRY(mapped(sc, &h_md, &d_md, (size_t)n_mdeltas * sizeof(kbg::MaskDelta)));
+  std::copy(mdeltas, mdeltas + n_mdeltas, h_md);
+  char* d_copy = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_copy, (const char*)nullptr, bytes + kProbeGuardBytes, kProbeSentinel));
+  PROBE_TRY(kbg::launch_apply(soa, d_nd, n_deltas, sc.stream));
+  PROBE_TRY(kbg::launch_mask_apply(d_mask, d_md, n_mdeltas, sc.stream));
+  PROBE_TRY(kbg::launch_copy16(d_copy, d, bytes / 16, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(nodes, d, bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(mask, d_mask, (size_t)mask_words * 8, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(copy_out, d_copy, bytes + kProbeGuardBytes, hipMemcpyDeviceToHost));
+  return 0;
+}
