@@ -494,7 +494,9 @@ enum {
    * change. Indices in a batch are those before the batch (new ones take the
    * next index of their kind, in event order); after the batch every kind is
    * renumbered — what left is dropped, the rest keeps its order, new ones
-   * last — and kbg_session_renumbering gives the old -> new maps. */
+   * last; tasks are renumbered in JobInfo.Tasks order grouped by job (ssn.Jobs
+   * order), so a caller must map every task index it keeps through
+   * KBG_RENUM_TASKS — and kbg_session_renumbering gives the old -> new maps. */
   KBG_EV_NODE_ADD = 6,     /* cache.AddNode of a node new to the cache (event_handlers.go:232-240, NewNodeInfo):
                               `node_spec`, `resource`, `max_task_num`, `unschedulable`; it joins ssn.Nodes last */
   KBG_EV_NODE_DELETE = 7,  /* cache.DeleteNode (event_handlers.go:262-268): node `node` leaves sc.Nodes with the
@@ -502,13 +504,38 @@ enum {
   KBG_EV_JOB_ADD = 8,      /* cache.AddPodGroup of a new job (event_handlers.go:344-358, setPodGroup): JobID
                               `name`, queue index `queue`, `min_available`, `creation_ns`, `priority`; it joins
                               ssn.Jobs last, its pods follow as KBG_EV_POD_ADD */
-  KBG_EV_JOB_DELETE = 9,   /* cache.DeletePodGroup (event_handlers.go:361-381, UnsetPodGroup): job `job` leaves
-                              ssn.Jobs; its pods stay on their nodes as pods outside the session jobs and its
-                              Running tasks join Session.Others (cache.go:570-582) */
+  KBG_EV_JOB_DELETE = 9,   /* cache.DeletePodGroup (event_handlers.go:361-381, UnsetPodGroup) or DeletePDB
+                              (:479-494, UnsetPDB) once the job holds neither: job `job` leaves ssn.Jobs; its
+                              pods stay on their nodes as pods outside the session jobs and its Running tasks
+                              join Session.Others (cache.go:570-582). While the other is left the job stays
+                              in ssn.Jobs as it is: no event */
   KBG_EV_QUEUE_ADD = 10,   /* cache.AddQueue (event_handlers.go:635-640): queue `name` with `weight` joins ssn.Queues
                               last */
-  KBG_EV_QUEUE_DELETE = 11 /* cache.DeleteQueue (event_handlers.go:650-654): queue `queue` leaves ssn.Queues, and
-                              every job of it leaves ssn.Jobs (cache.go:584-588; not into Others) */
+  KBG_EV_QUEUE_DELETE = 11, /* cache.DeleteQueue (event_handlers.go:650-654): queue `queue` leaves ssn.Queues, and
+                               every job of it leaves ssn.Jobs (cache.go:584-588; not into Others) */
+  /* Update events of jobs and queues the session holds. They are additive:
+   * kbg_event keeps its layout (every field they read exists since ABI 13) and
+   * KBG_ABI_VERSION stays 13; a library without them answers KBG_E_INVALID
+   * ("event kind"). KBG_EV_JOB_UPDATE and KBG_EV_QUEUE_SET are applied in
+   * place: nothing is renumbered (kbg_session_renumbering reports 0 for every
+   * kind) and the session is not rebuilt (kbg_stats.update_rebuilds stays).
+   * KBG_EV_QUEUE_UPDATE is structural. On a session sharded over a
+   * communicator all three are KBG_E_UNSUPPORTED, as structural events are. */
+  KBG_EV_JOB_UPDATE = 12,  /* cache.UpdatePodGroup / AddPodGroup / AddPDB / UpdatePDB of a JobID the session holds
+                              (event_handlers.go:344-363,458-476 -> SetPodGroup / SetPDB, job_info.go:166-200):
+                              job `job` takes `queue` (a live session queue), `min_available`, `creation_ns` and
+                              `priority`, as KBG_EV_JOB_ADD reads them; it keeps its place in ssn.Jobs and its
+                              tasks */
+  KBG_EV_QUEUE_SET = 13,   /* cache.AddQueue / AddNamespace of a UID the cache holds (sc.Queues[uid] = qi,
+                              event_handlers.go:635-640,726-736): queue `queue` takes `weight`, in its place */
+  KBG_EV_QUEUE_UPDATE = 14 /* cache.UpdateQueue / UpdateNamespace = deleteQueue + addQueue of the same name
+                              (event_handlers.go:642-647,738-743): queue `queue` takes `weight` and the last place
+                              in ssn.Queues (Go map order is insertion order here); its jobs stay (sc.Jobs is
+                              untouched; cache.go:584-588 filters at Snapshot time only). Within the batch index
+                              `queue` is dead from here on and the queue takes the next new queue index in event
+                              order, as a KBG_EV_QUEUE_ADD would: later events name it by that index. After the
+                              batch KBG_RENUM_QUEUES maps both the old index and that temporary one to the
+                              queue's final place */
 };
 /* The Node of a KBG_EV_NODE_SET event (strings are copied). */
 typedef struct kbg_node_spec {
@@ -523,9 +550,9 @@ typedef struct kbg_event {
   int32_t task;          /* POD_UPDATE / POD_DELETE */
   int32_t status;        /* POD_UPDATE / POD_ADD: TaskStatus (api/helpers.go:35-61) */
   int32_t node;          /* POD_UPDATE / POD_ADD: node index of NodeName or -1; NODE_UPDATE: the node */
-  int32_t job;           /* POD_ADD */
+  int32_t job;           /* POD_ADD; JOB_DELETE / JOB_UPDATE: the job */
   int32_t spec;          /* POD_ADD: index into the session's specs, -1 = none */
-  int32_t priority;      /* POD_ADD: TaskInfo.Priority */
+  int32_t priority;      /* POD_ADD: TaskInfo.Priority; JOB_ADD / JOB_UPDATE: JobInfo.Priority */
   int32_t max_task_num;  /* NODE_UPDATE */
   kbg_resource resource; /* POD_ADD: Resreq; NODE_UPDATE: Allocatable */
   int32_t unschedulable; /* NODE_UPDATE */
@@ -537,10 +564,10 @@ typedef struct kbg_event {
                             the cache knows only from pods (Node nil, Name ""); without it the session takes the
                             NodeName that node's session pods carry, and refuses one holding none */
   const char* name;      /* JOB_ADD: JobID "<namespace>/<podgroup>"; QUEUE_ADD: the queue's name */
-  int64_t creation_ns;   /* JOB_ADD: CreationTimestamp */
-  int32_t queue;         /* JOB_ADD: its queue; QUEUE_DELETE: the queue */
-  int32_t min_available; /* JOB_ADD: PodGroup.Spec.MinMember */
-  int32_t weight;        /* QUEUE_ADD: Queue.Spec.Weight */
+  int64_t creation_ns;   /* JOB_ADD / JOB_UPDATE: CreationTimestamp */
+  int32_t queue;         /* JOB_ADD / JOB_UPDATE: its queue; QUEUE_DELETE / QUEUE_SET / QUEUE_UPDATE: the queue */
+  int32_t min_available; /* JOB_ADD / JOB_UPDATE: PodGroup.Spec.MinMember (PDB: MinAvailable) */
+  int32_t weight;        /* QUEUE_ADD / QUEUE_SET / QUEUE_UPDATE: Queue.Spec.Weight (a namespace: 1) */
   int32_t reserved2;
 } kbg_event;
 /* Applies events[0..n) in order; the cycle state is reset as by
@@ -553,7 +580,9 @@ typedef struct kbg_event {
  * them that pod leaves the node as RemoveTask takes it), a KBG_EV_NODE_UPDATE
  * of a node the cache only knows from a pod (send KBG_EV_NODE_SET: the Node's
  * name, labels and taints), a KBG_EV_NODE_SET of such a node holding a pod
- * outside the session jobs without node_pods. KBG_E_REF_PANIC (the cache itself would
+ * outside the session jobs without node_pods, a KBG_EV_JOB_UPDATE / QUEUE_SET /
+ * QUEUE_UPDATE naming a job or queue that is out of range or was deleted
+ * earlier in the batch (KBG_E_INVALID). KBG_E_REF_PANIC (the cache itself would
  * panic: a Resource.Sub underflow in AddTask / RemoveTask / SetNode) is found
  * while the events are applied: the session is then unusable and every later
  * call on it but kbg_session_close returns KBG_E_INVALID (re-open it). */

@@ -41,6 +41,32 @@ int32_t append_str(Session& S, const char* v) {
   return id;
 }
 
+// What follows from the jobs' own fields (CreationTimestamp, Priority, queue;
+// job_rank is the bytewise UID order): JobOrderFn's fallback order, the dense
+// priority ranks and the packed queue of each job. At ingest, and again after
+// an update edited a job in place (KBG_EV_JOB_UPDATE).
+void rank_jobs(Session& S) {
+  std::vector<int32_t> order(S.n_jobs);
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    if (S.jobs_in[a].creation_ns != S.jobs_in[b].creation_ns) return S.jobs_in[a].creation_ns < S.jobs_in[b].creation_ns;
+    return S.job_rank[a] < S.job_rank[b];
+  });
+  S.job_frank.assign(S.n_jobs, 0);
+  for (int32_t i = 0; i < S.n_jobs; ++i) S.job_frank[order[i]] = i;
+  S.job_by_frank = order;
+  std::vector<int32_t> prios(S.n_jobs);
+  for (int32_t j = 0; j < S.n_jobs; ++j) prios[j] = S.jobs_in[j].priority;
+  std::sort(prios.begin(), prios.end(), std::greater<int32_t>());
+  prios.erase(std::unique(prios.begin(), prios.end()), prios.end());
+  S.job_prank.resize(S.n_jobs);
+  for (int32_t j = 0; j < S.n_jobs; ++j)
+    S.job_prank[j] = (uint32_t)(std::lower_bound(prios.begin(), prios.end(), S.jobs_in[j].priority,
+                                                 std::greater<int32_t>()) - prios.begin());
+  S.job_queue.resize(S.n_jobs);
+  for (int32_t j = 0; j < S.n_jobs; ++j) S.job_queue[j] = S.jobs_in[j].queue;
+}
+
 kbg_status ingest(Session& S, const kbg_snapshot* snap, const kbg_options* o) {
   static const bool prof = getenv("KBG_PROFILE_OPEN") != nullptr;
   auto tl = std::chrono::steady_clock::now();
@@ -260,7 +286,7 @@ kbg_status ingest(Session& S, const kbg_snapshot* snap, const kbg_options* o) {
     }
   }
 
-  // ---- job / queue ranks (jobs and queues do not change over a resident session)
+  // ---- job / queue ranks (the sets and UIDs do not change between rebuilds; a job's fields may: rank_jobs)
   {
     std::vector<int32_t> ids(S.n_jobs);
     for (int32_t j = 0; j < S.n_jobs; ++j) ids[j] = S.jobs_in[j].uid;
@@ -269,27 +295,7 @@ kbg_status ingest(Session& S, const kbg_snapshot* snap, const kbg_options* o) {
     for (int32_t q = 0; q < S.n_queues; ++q) ids[q] = S.queues_in[q].uid;
     S.queue_rank = ranks_of(S, ids);
   }
-  {
-    std::vector<int32_t> order(S.n_jobs);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-      if (S.jobs_in[a].creation_ns != S.jobs_in[b].creation_ns) return S.jobs_in[a].creation_ns < S.jobs_in[b].creation_ns;
-      return S.job_rank[a] < S.job_rank[b];
-    });
-    S.job_frank.assign(S.n_jobs, 0);
-    for (int32_t i = 0; i < S.n_jobs; ++i) S.job_frank[order[i]] = i;
-    S.job_by_frank = order;
-    std::vector<int32_t> prios(S.n_jobs);
-    for (int32_t j = 0; j < S.n_jobs; ++j) prios[j] = S.jobs_in[j].priority;
-    std::sort(prios.begin(), prios.end(), std::greater<int32_t>());
-    prios.erase(std::unique(prios.begin(), prios.end()), prios.end());
-    S.job_prank.resize(S.n_jobs);
-    for (int32_t j = 0; j < S.n_jobs; ++j)
-      S.job_prank[j] = (uint32_t)(std::lower_bound(prios.begin(), prios.end(), S.jobs_in[j].priority,
-                                                   std::greater<int32_t>()) - prios.begin());
-    S.job_queue.resize(S.n_jobs);
-    for (int32_t j = 0; j < S.n_jobs; ++j) S.job_queue[j] = S.jobs_in[j].queue;
-  }
+  rank_jobs(S);
   S.task_rank.clear();  // computed by derive_host
   phase("plugins+rest");
   return KBG_OK;

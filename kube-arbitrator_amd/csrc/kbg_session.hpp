@@ -535,6 +535,7 @@ struct Session {
   // kbg_session_renumbering; empty: nothing renumbered)
   bool adopt_strings = false;                         // ingest keeps strs / canon / canon_of (restructure)
   std::vector<uint8_t> node_dead, job_dead, queue_dead, job_to_others;
+  std::vector<int32_t> queue_next;                    // KBG_EV_QUEUE_UPDATE: dead queue index -> the index it took (-1: none)
   std::vector<int32_t> renum[4];
   std::vector<kbg_plugin_option> plugins_in;          // the snapshot's tier entries, for the rebuild
   std::vector<int32_t> tier_sizes_in;

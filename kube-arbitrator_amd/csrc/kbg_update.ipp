@@ -17,6 +17,8 @@ struct UpdateCtx {
   std::vector<int32_t> nodes;  // node rows to rewrite in HBM
   std::vector<uint8_t> seen;
   bool rebuild = false;        // the static masks must be recompiled
+  bool jobs_edited = false;    // a KBG_EV_JOB_UPDATE changed a job's fields: rank_jobs
+  bool job_moved = false;      // ... and its queue: the queues' running sums are summed again
   void touch(int32_t n) {
     if (!seen[n]) {
       seen[n] = 1;
@@ -365,12 +367,42 @@ kbg_status apply_node_set(Session& S, UpdateCtx& U, const kbg_event& e) {
   return KBG_OK;
 }
 
-// Structural events (kbgpu.h KBG_EV_NODE_ADD ... QUEUE_DELETE) on the inputs:
-// what joins is appended (its pod events in the same batch find it), what
-// leaves is marked; restructure() then rebuilds the session from the updated
-// snapshot. update_precheck has validated every field.
+// The kinds after which the session is rebuilt from its updated snapshot and
+// renumbered. KBG_EV_JOB_UPDATE and KBG_EV_QUEUE_SET are not among them: they
+// edit a job or queue in its place.
+bool structural_kind(int32_t kind) {
+  switch (kind) {
+    case KBG_EV_NODE_ADD:
+    case KBG_EV_NODE_DELETE:
+    case KBG_EV_JOB_ADD:
+    case KBG_EV_JOB_DELETE:
+    case KBG_EV_QUEUE_ADD:
+    case KBG_EV_QUEUE_DELETE:
+    case KBG_EV_QUEUE_UPDATE:
+      return true;
+  }
+  return false;
+}
+
+// Structural events (kbgpu.h KBG_EV_NODE_ADD ... QUEUE_DELETE, QUEUE_UPDATE)
+// on the inputs: what joins is appended (its pod events in the same batch find
+// it), what leaves is marked; restructure() then rebuilds the session from the
+// updated snapshot. update_precheck has validated every field.
 kbg_status apply_structural(Session& S, UpdateCtx& U, const kbg_event& e) {
   switch (e.kind) {
+    case KBG_EV_QUEUE_UPDATE: {  // deleteQueue + addQueue of the same name (event_handlers.go:642-647,738-743)
+      // the queue leaves its place and joins last, as a QUEUE_ADD would; sc.Jobs
+      // is untouched, so its jobs (those of this batch too) follow it
+      const int32_t q = S.n_queues++;
+      S.queues_in.push_back(kbg_queue{S.queues_in[e.queue].uid, e.weight});
+      S.queue_dead.push_back(0);
+      S.queue_dead[e.queue] = 1;
+      S.queue_next.resize(S.n_queues, -1);
+      S.queue_next[e.queue] = q;
+      for (int32_t j = 0; j < S.n_jobs; ++j)
+        if (S.jobs_in[j].queue == e.queue) S.jobs_in[j].queue = q;
+      return KBG_OK;
+    }
     case KBG_EV_NODE_ADD: {  // cache.AddNode of a new name -> NewNodeInfo (event_handlers.go:232-240)
       kbg_node nd{};
       const int32_t n = S.n_nodes++;
@@ -521,7 +553,24 @@ kbg_status apply_event(Session& S, UpdateCtx& U, const kbg_event& e, const uint6
     case KBG_EV_JOB_DELETE:
     case KBG_EV_QUEUE_ADD:
     case KBG_EV_QUEUE_DELETE:
+    case KBG_EV_QUEUE_UPDATE:
       return apply_structural(S, U, e);
+    case KBG_EV_JOB_UPDATE: {  // SetPodGroup / SetPDB on a job the session holds (job_info.go:166-200)
+      if (e.job < 0 || e.job >= S.n_jobs || e.queue < 0 || e.queue >= S.n_queues)
+        return fail(KBG_E_INVALID, "JOB_UPDATE event (job, queue)");
+      kbg_job& j = S.jobs_in[e.job];  // its place in ssn.Jobs and its tasks stay
+      U.job_moved |= j.queue != e.queue;
+      j.queue = e.queue;
+      j.min_available = e.min_available;
+      j.priority = e.priority;
+      j.creation_ns = e.creation_ns;
+      U.jobs_edited = true;
+      return KBG_OK;
+    }
+    case KBG_EV_QUEUE_SET:  // sc.Queues[uid] = qi of a UID the cache holds: the weight, in place
+      if (e.queue < 0 || e.queue >= S.n_queues) return fail(KBG_E_INVALID, "QUEUE_SET event queue");
+      S.queues_in[e.queue].weight = e.weight;
+      return KBG_OK;
     case KBG_EV_NODE_UPDATE: {
       if (e.node < 0 || e.node >= S.n_nodes) return fail(KBG_E_INVALID, "event node index");
       kbg_node& nd = S.nodes_in[e.node];
@@ -557,14 +606,16 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
   auto status_ok = [](int32_t st) { return st > 0 && st <= KBG_UNKNOWN && !(st & (st - 1)); };
   bool port_specs = false;
   for (const kbg_spec& sp : S.specs_in) port_specs |= sp.has_host_ports != 0;
-  bool structural = false;
+  bool structural = false, edits = false;  // edits: a job or queue changed in place (JOB_UPDATE, QUEUE_SET)
   int32_t adds = 0;
   for (int32_t i = 0; i < n; ++i) {
     adds += ev[i].kind == KBG_EV_POD_ADD;
-    structural |= ev[i].kind >= KBG_EV_NODE_ADD;
+    structural |= structural_kind(ev[i].kind);
+    edits |= ev[i].kind == KBG_EV_JOB_UPDATE || ev[i].kind == KBG_EV_QUEUE_SET;
   }
-  if (structural && S.comm)
-    return fail(KBG_E_UNSUPPORTED, "structural events on a session sharded over a communicator: re-open it on every rank");
+  if ((structural || edits) && S.comm)
+    return fail(KBG_E_UNSUPPORTED, "structural events and job / queue updates on a session sharded over a communicator: "
+                                   "re-open it on every rank");
   // else no removal can be refused (a structural batch walks every pod's node: pods on deleted nodes)
   const bool holders = port_specs || !S.outsiders.empty() || structural;
   const int32_t T0 = S.n_tasks;
@@ -607,7 +658,11 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
     for (int32_t q = 0; q < Q; ++q) queue_of_uid.emplace(S.canon[S.queues_in[q].uid], q);
   }
   auto task_job = [&](int32_t t) { return t < T0 ? S.tasks_in[t].job : add_job[t - T0]; };
-  auto job_queue_of = [&](int32_t j) { return j < S.n_jobs ? S.jobs_in[j].queue : jq[j - S.n_jobs]; };
+  std::unordered_map<int32_t, int32_t> jq_now;  // jobs an earlier JOB_UPDATE / QUEUE_UPDATE of the batch moved
+  auto job_queue_of = [&](int32_t j) {
+    if (auto it = jq_now.find(j); it != jq_now.end()) return it->second;
+    return j < S.n_jobs ? S.jobs_in[j].queue : jq[j - S.n_jobs];
+  };
   // a live name among the session's (or the batch's) nodes, jobs or queues
   auto node_live = [&](const std::string& nm) {
     if (auto b = bnodes.find(nm); b != bnodes.end()) return b->second >= 0;
@@ -829,6 +884,36 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
           }
         break;
       }
+      case KBG_EV_JOB_UPDATE:  // (a batch without structural events has deleted nothing)
+        if (e.job < 0 || e.job >= J || (structural && jdead[e.job]))
+          return fail(KBG_E_INVALID, "JOB_UPDATE event job (out of range, or deleted earlier in the batch)");
+        if (e.queue < 0 || e.queue >= Q || (structural && qdead[e.queue]))
+          return fail(KBG_E_INVALID, "JOB_UPDATE event queue (out of range, or dead in the batch)");
+        jq_now[e.job] = e.queue;
+        break;
+      case KBG_EV_QUEUE_SET:
+        if (e.queue < 0 || e.queue >= Q || (structural && qdead[e.queue]))
+          return fail(KBG_E_INVALID, "QUEUE_SET event queue (out of range, or deleted earlier in the batch)");
+        break;
+      case KBG_EV_QUEUE_UPDATE: {
+        if (e.queue < 0 || e.queue >= Q || qdead[e.queue])
+          return fail(KBG_E_INVALID, "QUEUE_UPDATE event queue (out of range, or deleted earlier in the batch)");
+        // delete + add of the same name: the index is dead, the name lives on under the next new index
+        std::string nm;
+        if (e.queue < S.n_queues) {
+          nm = S.strs[S.queues_in[e.queue].uid];
+        } else {
+          for (const auto& [bn, q] : bqueues)
+            if (q == e.queue) nm = bn;
+        }
+        qdead[e.queue] = 1;
+        bqueues[nm] = Q;
+        qdead.push_back(0);
+        for (int32_t j = 0; j < J; ++j)  // sc.Jobs is untouched: its jobs follow it
+          if (job_queue_of(j) == e.queue) jq_now[j] = Q;
+        ++Q;
+        break;
+      }
       default:
         return fail(KBG_E_INVALID, "event kind");
     }
@@ -870,6 +955,13 @@ kbg_status rebuild_snapshot(const Session& S, Rebuilt& B) {
       rq[q] = (int32_t)queues.size();
       queues.push_back(S.queues_in[q]);
     }
+  // a queue a QUEUE_UPDATE moved: its old index (and each temporary one, when
+  // the batch updated it again) maps to its final place
+  for (int32_t q = 0; q < Q && q < (int32_t)S.queue_next.size(); ++q) {
+    int32_t to = S.queue_next[q];
+    while (to >= 0 && to < (int32_t)S.queue_next.size() && S.queue_next[to] >= 0) to = S.queue_next[to];
+    if (to >= 0) rq[q] = rq[to];
+  }
   std::vector<kbg_job>& jobs = B.jobs;
   std::vector<kbg_task>& tasks = B.tasks;
   std::vector<kbg_resource>& others = B.others;
@@ -1099,12 +1191,13 @@ kbg_status session_update(Session& S, const kbg_event* ev, int32_t n) {
   const auto t0 = std::chrono::steady_clock::now();
   for (auto& r : S.renum) r.clear();
   bool structural = false;
-  for (int32_t i = 0; i < n; ++i) structural |= ev[i].kind >= KBG_EV_NODE_ADD;
+  for (int32_t i = 0; i < n; ++i) structural |= structural_kind(ev[i].kind);
   if (structural) {
     S.node_dead.assign(S.n_nodes, 0);
     S.job_dead.assign(S.n_jobs, 0);
     S.job_to_others.assign(S.n_jobs, 0);
     S.queue_dead.assign(S.n_queues, 0);
+    S.queue_next.assign(S.n_queues, -1);
   }
   if (n < 0 || (n > 0 && !ev)) return fail(KBG_E_INVALID, "events");
   // the cycle state goes back to "just opened"
@@ -1224,7 +1317,17 @@ kbg_status session_update(Session& S, const kbg_event* ev, int32_t n) {
     S.stats.update_rebuilds = S.rebuilds;
     return KBG_OK;
   }
-  S.vt_stale = true;
+  if (U.jobs_edited) {
+    // a job's fields changed in place: JobOrderFn's ranks and the packed
+    // queues follow them, and when a job changed its queue the queues'
+    // running sums (keyed by each task's queue at the time it was added) are
+    // summed again by the derive; the rest of what depends on them — job_min,
+    // the queues' attrs in order of first job, the water-fill, the job heaps
+    // — every derive recomputes
+    rank_jobs(S);
+    if (U.job_moved) S.prop_sums_ok = false;
+  }
+  S.vt_stale = true;  // (also the victim tables' job queues, MinAvailable and deserved shares)
   S.vc.valid = false;
   const bool had_masks = S.has_ports || S.has_aff;
   kbg_status st = KBG_OK;

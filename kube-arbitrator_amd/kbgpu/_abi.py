@@ -190,6 +190,12 @@ EV_JOB_ADD = 8
 EV_JOB_DELETE = 9
 EV_QUEUE_ADD = 10
 EV_QUEUE_DELETE = 11
+EV_JOB_UPDATE = 12  # in place (additive: kbg_event's layout and ABI_VERSION 13 stay)
+EV_QUEUE_SET = 13  # in place
+EV_QUEUE_UPDATE = 14  # structural: the queue takes the last place
+# the kinds after which the library rebuilds and renumbers the session (kbg_session_renumbering)
+STRUCTURAL_EVENTS = frozenset((EV_NODE_ADD, EV_NODE_DELETE, EV_JOB_ADD, EV_JOB_DELETE, EV_QUEUE_ADD, EV_QUEUE_DELETE,
+                               EV_QUEUE_UPDATE))
 RENUM_TASKS, RENUM_NODES, RENUM_JOBS, RENUM_QUEUES = 0, 1, 2, 3
 
 

@@ -2,7 +2,8 @@
 
 Mirrors the parts of pkg/scheduler/cache that define a session's contents:
 AddNode/AddPod/AddPodGroup/AddPDB/AddQueue/AddNamespace
-(event_handlers.go:40-61,232-240,344-358,458-470,635-640,726-736) and
+(event_handlers.go:40-61,232-240,344-358,458-470,635-640,726-736), their
+Update / Delete counterparts (:361-381,406-427,474-494,642-654,738-755) and
 Snapshot (cache.go:549-597). Informers, resync and the apiserver are out of
 scope; Bind goes to a caller-supplied binder (allocate_test.go:99-115 style).
 Go map iteration order is replaced by insertion order.
@@ -115,18 +116,44 @@ class SchedulerCache:
             self.jobs[jid] = JobInfo(jid)
         self.jobs[jid].set_pod_group(pg, self.default_queue)
 
+    def update_pod_group(self, pg):
+        # :361-363,406-427: updatePodGroup is setPodGroup(new). UpdatePodGroup does
+        # not blank .spec.queue under namespace-as-queue, which AddPodGroup
+        # (:392-395) does; this mirror blanks it in neither (the fixtures'
+        # namespace-as-queue PodGroups name no queue), so both are setPodGroup.
+        self.add_pod_group(pg)
+
     def add_pdb(self, pdb):  # :458-470
         jid = pdb.get("controller", "")
         if jid not in self.jobs:
             self.jobs[jid] = JobInfo(jid)
         self.jobs[jid].set_pdb(pdb, self.default_queue)
 
+    def update_pdb(self, pdb):  # :474-476: updatePDB is setPDB(new)
+        self.add_pdb(pdb)
+
+    def delete_pdb(self, pdb):  # :479-494: UnsetPDB; the job stays while it has a PodGroup or pods (cache.go:570-582)
+        job = self.jobs.get(pdb.get("controller", ""))
+        if job is not None:
+            job.pdb = None
+
     def add_queue(self, q):  # :635-640
         qi = QueueInfo(q["name"], q.get("weight", 0))
         self.queues[qi.uid] = qi
 
+    def update_queue(self, q):  # :642-647: deleteQueue(old) + addQueue(new): it takes the last place
+        self.delete_queue(q)
+        self.add_queue(q)
+
     def add_namespace(self, name):  # :726-736
         self.queues[name] = QueueInfo(name, 1)
+
+    def update_namespace(self, name):  # :738-743: deleteNamespace(old) + addNamespace(new), weight 1
+        self.delete_namespace(name)
+        self.add_namespace(name)
+
+    def delete_namespace(self, name):  # :745-755
+        self.queues.pop(name, None)
 
     def bind(self, task, hostname):  # cache.go:408-444 (session-visible part)
         self.binder.bind(task.pod, hostname)

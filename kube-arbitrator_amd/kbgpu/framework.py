@@ -47,6 +47,13 @@ def get_action(name):  # plugins.go:60-66
     return _actions.get(name)
 
 
+def _copy_job_fields(src, dst):
+    """What SetPodGroup / SetPDB / UnsetPodGroup / UnsetPDB write (job_info.go:166-226)."""
+    for k in ("name", "namespace", "queue", "priority", "min_available", "creation_timestamp", "pod_group", "pdb"):
+        setattr(dst, k, getattr(src, k))
+    return dst
+
+
 class Session:
     """framework.Session (session.go:35-61) plus the device handle."""
 
@@ -151,16 +158,23 @@ class Session:
         applied to the resident session (include/kbgpu.h). `changes` is a list
         of ("pod_update", pod) | ("pod_delete", pod) | ("pod_add", pod) |
         ("node_add", node) | ("node_update", node) | ("node_delete", node) |
-        ("pod_group_add", pg) | ("pod_group_delete", pg) | ("queue_add", q) |
-        ("queue_delete", q) in event order, objects as the informer delivers
+        ("pod_group_add", pg) | ("pod_group_update", pg) | ("pod_group_delete", pg) |
+        ("pdb_add", pdb) | ("pdb_update", pdb) | ("pdb_delete", pdb) |
+        ("queue_add", q) | ("queue_update", q) | ("queue_delete", q) |
+        ("namespace_add", ns) | ("namespace_update", ns) | ("namespace_delete", ns)
+        in event order, objects as the informer delivers
         them (event_handlers.go). New pods must use a pod spec the session
         already has. Structural changes (a node, PodGroup or queue joins or
-        leaves; a pod naming a node the cache does not know, which makes a
-        NodeInfo(nil), event_handlers.go:49-53) renumber the session: the
-        wrapper's task, node, job and queue lists follow the library's
-        renumbering (kbg_session_renumbering). The host-side objects are not
-        replayed: read results through the C ABI (decisions, job / queue /
-        node state)."""
+        leaves, a queue is updated: delete + add; a pod naming a node the cache
+        does not know, which makes a NodeInfo(nil), event_handlers.go:49-53)
+        renumber the session: the wrapper's task, node, job and queue lists
+        follow the library's renumbering (kbg_session_renumbering). A PodGroup
+        or PDB set on a session job (KBG_EV_JOB_UPDATE) and a queue added again
+        under a UID the session holds (KBG_EV_QUEUE_SET) change it in place.
+        The wrapper's JobInfo / QueueInfo objects follow the events (pod_group,
+        pdb, min_available, queue, weight) once the library took the batch;
+        the host-side task and node objects are not replayed: read results
+        through the C ABI (decisions, job / queue / node state)."""
         plan = self.marshal(changes)
         _abi.check(_abi.lib().kbg_session_update(self.handle, plan.evs, plan.n_ev))
         self._accept(plan)
@@ -186,6 +200,12 @@ class Session:
         objs = {}  # task index -> its TaskInfo after the events (applied once the library accepts them)
         n_objs = len(flat.task_objs)
         renamed = {}  # pod-only node index -> the name its Node gave it
+        # wrapper state the events change, applied in _accept once the library took the batch:
+        job_edits = {}  # session job index -> a JobInfo holding its fields after the events
+        queue_weights = {}  # session queue index -> its weight after the events
+        queue_moved = {}  # queue index a queue_update killed -> the index the queue took
+        outside = set()  # JobIDs whose pods stay in the cache outside the session jobs
+        default_queue = getattr(self.cache, "default_queue", "")
 
         def ev():
             nonlocal n_ev
@@ -193,7 +213,57 @@ class Session:
             return evs[n_ev - 1]
 
         def job_of(j):
+            if j in job_edits:
+                return job_edits[j]
             return self.jobs[j] if j < len(self.jobs) else new_jobs[j]
+
+        def job_edit(j):
+            """Job j's fields to write: a job this batch added is the plan's own
+            object; a session job gets a copy that _accept writes back."""
+            if j >= len(self.jobs):
+                return new_jobs[j]
+            if j not in job_edits:
+                job_edits[j] = _copy_job_fields(self.jobs[j], JobInfo(self.jobs[j].uid))
+            return job_edits[j]
+
+        def job_update(j, job):
+            """KBG_EV_JOB_UPDATE: session job j takes SetPodGroup's / SetPDB's fields."""
+            if job.queue not in qidx:
+                raise ValueError(f"job {job.uid!r}: queue {job.queue!r} is not a session queue (re-open when it "
+                                 "exists)")
+            e = ev()
+            e.kind, e.job = _abi.EV_JOB_UPDATE, j
+            e.queue = qidx[job.queue]
+            e.min_available = job.min_available
+            e.priority = job.priority
+            e.creation_ns = job.creation_timestamp
+
+        def job_add(job):
+            """KBG_EV_JOB_ADD of a JobID new to the cache (NewJobInfo + SetPodGroup / SetPDB)."""
+            nonlocal n_jobs
+            if job.queue not in qidx:
+                raise ValueError(f"job {job.uid!r}: queue {job.queue!r} is not a session queue (re-open when it "
+                                 "exists)")
+            e = ev()
+            e.kind = _abi.EV_JOB_ADD
+            keep.append(job.uid.encode())
+            e.name = keep[-1]
+            e.queue = qidx[job.queue]
+            e.min_available = job.min_available
+            e.priority = job.priority
+            e.creation_ns = job.creation_timestamp
+            jidx[job.uid] = n_jobs
+            new_jobs[n_jobs] = job
+            n_jobs += 1
+
+        def job_delete(jid):
+            """KBG_EV_JOB_DELETE: neither a PodGroup nor a PDB is left (cache.go:570-582)."""
+            e = ev()
+            e.kind, e.job = _abi.EV_JOB_DELETE, jidx.pop(jid)
+            outside.add(jid)  # its pods stay in the cache, outside the session jobs
+
+        def outside_job(jid):
+            return jid in outside or jid in self._outside_jobs()
 
         def node_spec(e, obj):
             ni = NodeInfo(obj)
@@ -236,6 +306,9 @@ class Session:
                 e.node_name = keep[-1]
 
         for kind, obj in changes:
+            if kind.startswith("namespace_"):  # a namespace used as a queue: its name, weight 1 (:726-755)
+                kind = "queue_" + kind[len("namespace_"):]
+                obj = {"name": obj if isinstance(obj, str) else obj["name"], "weight": 1}
             if kind in ("node_update", "node_add"):
                 # cache.AddNode / UpdateNode -> SetNode with the whole Node (the library
                 # compares labels and taints and rebuilds only when they change)
@@ -281,38 +354,53 @@ class Session:
                 e = ev()
                 e.kind, e.node = _abi.EV_NODE_DELETE, idx
                 continue
-            if kind in ("pod_group_add", "pod_group_delete"):
+            if kind in ("pod_group_add", "pod_group_update", "pod_group_delete"):
                 jid = f"{obj.get('namespace', '')}/{obj['name']}"
-                if kind == "pod_group_delete":  # UnsetPodGroup: the job leaves ssn.Jobs
-                    j = jidx.pop(jid, None)
+                if kind == "pod_group_delete":  # UnsetPodGroup: the job leaves ssn.Jobs unless a PDB keeps it
+                    j = jidx.get(jid)
                     if j is not None:
-                        e = ev()
-                        e.kind, e.job = _abi.EV_JOB_DELETE, j
-                        self._outside_jobs().add(jid)  # its pods stay in the cache, outside the session jobs
+                        if job_of(j).pdb is not None:
+                            job_edit(j).pod_group = None  # it stays in ssn.Jobs, its fields as they are (cache.go:570)
+                        else:
+                            job_delete(jid)
                     continue
-                if jid in jidx:
-                    raise ValueError(f"PodGroup {jid!r}: an update of a session job's PodGroup needs a re-open")
-                if jid in self._outside_jobs():
+                if jid in jidx:  # setPodGroup on a job the session holds (:344-363): in place
+                    job = job_edit(jidx[jid])
+                    job.set_pod_group(obj, default_queue)
+                    job_update(jidx[jid], job)
+                    continue
+                if outside_job(jid):
                     raise ValueError(f"PodGroup {jid!r}: the cache holds pods of it outside the session jobs "
                                      "(they predate the PodGroup): re-open")
                 job = JobInfo(jid)
-                job.set_pod_group(obj, getattr(self.cache, "default_queue", ""))
-                if job.queue not in qidx:
-                    raise ValueError(f"PodGroup {jid!r}: queue {job.queue!r} is not a session queue (re-open when it "
-                                     "exists)")
-                e = ev()
-                e.kind = _abi.EV_JOB_ADD
-                keep.append(jid.encode())
-                e.name = keep[-1]
-                e.queue = qidx[job.queue]
-                e.min_available = job.min_available
-                e.priority = job.priority
-                e.creation_ns = job.creation_timestamp
-                jidx[jid] = n_jobs
-                new_jobs[n_jobs] = job
-                n_jobs += 1
+                job.set_pod_group(obj, default_queue)
+                job_add(job)
                 continue
-            if kind in ("queue_add", "queue_delete"):
+            if kind in ("pdb_add", "pdb_update", "pdb_delete"):
+                jid = obj.get("controller", "")  # the JobID is the PDB's controller (:458-494)
+                if not jid:  # "the controller of PodDisruptionBudget is empty": the handler returns an error
+                    continue
+                if kind == "pdb_delete":  # UnsetPDB: the job stays in ssn.Jobs while it has a PodGroup
+                    j = jidx.get(jid)
+                    if j is not None:
+                        if job_of(j).pod_group is not None:
+                            job_edit(j).pdb = None
+                        else:
+                            job_delete(jid)
+                    continue
+                if jid in jidx:  # setPDB on a job the session holds: in place
+                    job = job_edit(jidx[jid])
+                    job.set_pdb(obj, default_queue)
+                    job_update(jidx[jid], job)
+                    continue
+                if outside_job(jid):
+                    raise ValueError(f"PodDisruptionBudget of {jid!r}: the cache holds pods of it outside the session "
+                                     "jobs (they predate the PDB): re-open")
+                job = JobInfo(jid)
+                job.set_pdb(obj, default_queue)
+                job_add(job)
+                continue
+            if kind in ("queue_add", "queue_update", "queue_delete"):
                 qi = QueueInfo(obj["name"], obj.get("weight", 0))
                 if kind == "queue_delete":
                     q = qidx.pop(qi.uid, None)
@@ -321,14 +409,25 @@ class Session:
                         e.kind, e.queue = _abi.EV_QUEUE_DELETE, q
                         for jid in [k for k, j in jidx.items() if job_of(j).queue == qi.uid]:
                             jidx.pop(jid)  # its jobs leave ssn.Jobs (cache.go:584-588)
-                            self._outside_jobs().add(jid)
+                            outside.add(jid)
                     continue
-                if qi.uid in qidx:
-                    raise ValueError(f"queue {qi.uid!r}: an update of a session queue needs a re-open")
+                q = qidx.get(qi.uid)
+                if q is not None and kind == "queue_add":  # sc.Queues[uid] = qi of a UID the cache holds: in place
+                    e = ev()
+                    e.kind, e.queue, e.weight = _abi.EV_QUEUE_SET, q, qi.weight
+                    if q < len(self.queues):
+                        queue_weights[q] = qi.weight
+                    else:
+                        new_queues[q].weight = qi.weight
+                    continue
                 e = ev()
-                e.kind = _abi.EV_QUEUE_ADD
-                keep.append(qi.uid.encode())
-                e.name = keep[-1]
+                if q is not None:  # updateQueue: deleteQueue + addQueue, the queue takes the last place; its jobs stay
+                    e.kind, e.queue = _abi.EV_QUEUE_UPDATE, q
+                    queue_moved[q] = n_queues
+                else:  # (an update of a queue the cache does not hold deletes nothing and adds it)
+                    e.kind = _abi.EV_QUEUE_ADD
+                    keep.append(qi.uid.encode())
+                    e.name = keep[-1]
                 e.weight = qi.weight
                 qidx[qi.uid] = n_queues
                 new_queues[n_queues] = qi
@@ -365,11 +464,15 @@ class Session:
             else:
                 raise ValueError(f"unknown change {kind}")
         return SimpleNamespace(evs=evs, n_ev=n_ev, keep=keep, objs=objs, n_objs=n_objs, renamed=renamed, tidx=tidx,
-                               new_nodes=new_nodes, new_jobs=new_jobs, new_queues=new_queues, pod_only=pod_only)
+                               new_nodes=new_nodes, new_jobs=new_jobs, new_queues=new_queues, pod_only=pod_only,
+                               job_edits=job_edits, queue_weights=queue_weights, queue_moved=queue_moved,
+                               outside=outside)
 
-    def _accept(self, plan):
+    def _accept(self, plan, maps=None):
         """update's second half, once the library applied the batch: the
-        wrapper's lists follow it (renumbered after a structural batch)."""
+        wrapper's jobs and queues take the events' fields and its lists follow
+        the library's (renumbered after a structural batch; `maps`: the four
+        renumbering maps when the caller has them, as the CPU tests do)."""
         flat = self.flat
         evs, n_ev, objs, n_objs, tidx = plan.evs, plan.n_ev, plan.objs, plan.n_objs, plan.tidx
         new_nodes, new_jobs, new_queues, pod_only = plan.new_nodes, plan.new_jobs, plan.new_queues, plan.pod_only
@@ -381,9 +484,16 @@ class Session:
         task_objs = flat.task_objs + [None] * (n_objs - len(flat.task_objs))
         for i, ti in objs.items():
             task_objs[i] = ti
-        structural = any(evs[k].kind >= _abi.EV_NODE_ADD for k in range(n_ev))
-        if structural:
-            self._renumber(task_objs, new_nodes, new_jobs, new_queues, pod_only)
+        # the wrapper's jobs and queues follow the events (only here: a refused batch changes nothing)
+        for j, job in plan.job_edits.items():
+            _copy_job_fields(job, self.jobs[j])
+        for q, weight in plan.queue_weights.items():
+            self.queues[q].weight = weight
+        self._outside_jobs().update(plan.outside)
+        structural = any(evs[k].kind in _abi.STRUCTURAL_EVENTS for k in range(n_ev))
+        if structural or maps is not None:
+            self._renumber(task_objs, new_nodes, new_jobs, new_queues, pod_only, maps=maps,
+                           queue_moved=plan.queue_moved)
         else:
             flat.task_objs = task_objs
         from .api import PENDING
@@ -402,9 +512,11 @@ class Session:
             self._outside = out
         return self._outside
 
-    def _renumber(self, task_objs, new_nodes, new_jobs, new_queues, pod_only, maps=None):
+    def _renumber(self, task_objs, new_nodes, new_jobs, new_queues, pod_only, maps=None, queue_moved=None):
         """The wrapper's lists after a structural update, by the library's
-        old -> new index maps (kbg_session_renumbering; `maps`: given)."""
+        old -> new index maps (kbg_session_renumbering; `maps`: given).
+        `queue_moved`: the queues a queue_update moved (dead index -> the index
+        the queue took; KBG_RENUM_QUEUES maps both to its final place)."""
         L = _abi.lib()
         flat = self.flat
 
@@ -444,6 +556,8 @@ class Session:
         self.job_index = {j.uid: j for j in self.jobs}
         flat.job_index = {j.uid: i for i, j in enumerate(self.jobs)}
         queues = list(self.queues) + [new_queues[i] for i in sorted(new_queues)]
+        for old in sorted(queue_moved or {}, reverse=True):  # the dead index holds the queue as it is now
+            queues[old] = queues[queue_moved[old]]
         self.queues = remap(queues, rq)
         self.queue_index = {q.uid: q for q in self.queues}
         flat.queue_index = {q.uid: i for i, q in enumerate(self.queues)}

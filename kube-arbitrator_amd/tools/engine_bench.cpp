@@ -92,7 +92,9 @@ extern "C" int32_t kbg_tool_update_nodes(const kbg_snapshot* snap, const kbg_opt
   return outcome;
 }
 
-// Structural events (kbg_session_update KBG_EV_NODE_ADD ... QUEUE_DELETE)
+// Structural events (kbg_session_update KBG_EV_NODE_ADD ... QUEUE_DELETE,
+// QUEUE_UPDATE) and the in-place ones (JOB_UPDATE, QUEUE_SET: the snapshot is
+// rebuilt after any batch, so the edited jobs and queues show in it too)
 // without a device: the session's host state opened from the snapshot, the
 // batch prechecked and applied as the library does, then the updated snapshot
 // the library would open from (rebuild_snapshot), encoded in the wire format
@@ -115,6 +117,7 @@ extern "C" int32_t kbg_tool_structural(const kbg_snapshot* snap, const kbg_optio
   S.job_dead.assign(S.n_jobs, 0);
   S.job_to_others.assign(S.n_jobs, 0);
   S.queue_dead.assign(S.n_queues, 0);
+  S.queue_next.assign(S.n_queues, -1);
   UpdateCtx U;
   U.seen.assign(S.n_nodes, 0);
   S.jmove_defer = (int64_t)n * 8 > (int64_t)S.n_tasks;
