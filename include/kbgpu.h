@@ -265,7 +265,10 @@ typedef struct kbg_options {
                            multi-GPU path, for single-device parity runs); with one (see
                            kbg_session_open_sharded) it must equal the communicator size. */
   int32_t plugin_registry; /* 1 = kbg_plugin_option.flags carry KBG_PLUGIN_REGISTERED (framework.go:30-35) */
-  int32_t reserved[5];
+  int32_t reasons;      /* 1 = kbg_allocate also computes, with the FitError counts, the per-predicate
+                           unschedulable reasons kbg_job_reasons_get returns (0: nothing is computed
+                           or allocated for them) */
+  int32_t reserved[4];
 } kbg_options;
 
 /* One placement decision, in reference order. */
@@ -615,6 +618,49 @@ kbg_status kbg_apply(kbg_session* s, int32_t node, const kbg_resource* req, int3
 
 kbg_status kbg_job_state_get(kbg_session* s, int32_t job, kbg_job_state* out);
 kbg_status kbg_queue_state_get(kbg_session* s, int32_t queue, kbg_queue_state* out);
+
+/* Why the nodes turned a not-ready job's last evaluated task away before the
+ * resource fit: the predicates plugin returns at the first failing stage
+ * (predicates.go:121-201) and allocate only logs the error (allocate.go:124-128).
+ * For the task FitError describes (job_info.go:329-358), at the same evaluation
+ * point (the decisions at or after `before` undone), every live node the
+ * reference's loop visited is counted under the FIRST stage that fails, in the
+ * reference's order:
+ *   0 KBG_WHY_POD_CAP        MaxTaskNum <= len(pods) then        predicates.go:125-127
+ *   1 KBG_WHY_SELECTOR       node selector + required node affinity       :129-141
+ *   2 KBG_WHY_HOST_PORTS     host ports, as at the evaluation point       :143-155
+ *   3 KBG_WHY_UNSCHEDULABLE  Spec.Unschedulable                           :157-169
+ *   4 KBG_WHY_TAINTS         taints / tolerations                         :171-183
+ *   5 KBG_WHY_POD_AFFINITY   inter-pod (anti)affinity, podLister Filter   :185-198
+ * A stage whose predicate returns an error counts under that stage. Deleted
+ * nodes are not in ssn.Nodes and count nowhere. With the predicates plugin off
+ * all six counts are zero. The visited nodes are [0, k] when the task was
+ * placed (Allocate) or pipelined at node k, every node otherwise. A node that
+ * passes all six stages is an entry of NodesFitDelta (fit_nodes) or the node
+ * the task was allocated to, so on sessions without nil Nodes
+ *   sum(count) + fit_nodes + (allocated ? 1 : 0) == visited. */
+enum {
+  KBG_WHY_POD_CAP = 0,
+  KBG_WHY_SELECTOR = 1,
+  KBG_WHY_HOST_PORTS = 2,
+  KBG_WHY_UNSCHEDULABLE = 3,
+  KBG_WHY_TAINTS = 4,
+  KBG_WHY_POD_AFFINITY = 5,
+  KBG_WHY_COUNT = 6
+};
+typedef struct kbg_job_reasons {
+  int32_t valid;         /* 0 for ready jobs and jobs never evaluated: nothing below is set */
+  int32_t task;          /* the task described (index into snapshot tasks) */
+  int32_t before;        /* its position in the decision log: decisions [0, before) were applied */
+  int32_t visited;       /* live nodes the reference's loop visited */
+  int32_t count[6];      /* nodes per reason (KBG_WHY_*) */
+  int32_t first_node[6]; /* lowest node index per reason, -1 when none */
+  int32_t reserved[2];
+} kbg_job_reasons;
+/* After kbg_allocate on a session opened with kbg_options.reasons = 1
+ * (KBG_E_INVALID otherwise). Sessions over a communicator are
+ * KBG_E_UNSUPPORTED; sessions whose shards are all local work. */
+kbg_status kbg_job_reasons_get(kbg_session* s, int32_t job, kbg_job_reasons* out);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

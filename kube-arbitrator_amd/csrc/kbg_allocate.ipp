@@ -303,8 +303,39 @@ struct LastEval {
 // mask plus the pod cap (no host ports, no pod affinity, no nil Node) and
 // whose whole node table is local.
 kbg_status svc_sum_counts(Session& S, int32_t* counts, size_t n);
+
+// kbg_options.reasons: the static predicate split by stage (kbg::StagePlanes),
+// built by kbg_stage_mask_kernel from the session's static tables at the first
+// cycle that asks and kept on both sides until the tables are rebuilt
+// (free_device). A session without a device gets h_stage from its opener.
+kbg_status ensure_stage_planes(Session& S) {
+  if (S.stage_valid) return KBG_OK;
+  if (!S.stream) return fail(KBG_E_INVALID, "internal: no stage planes on a session without a device");
+  using clk = std::chrono::steady_clock;
+  auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+  const bool prof = getenv("KBG_PROFILE_REASONS") != nullptr;
+  const auto t0 = clk::now();
+  const size_t words = kbg::kbg_stage_words(S.n_classes, S.W);
+  if (!S.d_stage)
+    if (kbg_status st = dalloc(S, &S.d_stage, words); st != KBG_OK) return st;
+  const auto t1 = clk::now();
+  HIP_TRY(kbg::launch_build_stage_planes(S.static_tab, S.n_classes, S.W,
+                                         kbg::kbg_stage_planes(S.d_stage, S.n_classes, S.W), S.stream));
+  if (prof) HIP_TRY(hipStreamSynchronize(S.stream));  // (the kernel apart from the download)
+  const auto t2 = clk::now();
+  S.h_stage.resize(words);
+  HIP_TRY(hipMemcpyAsync(S.h_stage.data(), S.d_stage, words * 8, hipMemcpyDeviceToHost, S.stream));
+  HIP_TRY(hipStreamSynchronize(S.stream));
+  S.stage_valid = true;
+  if (prof)
+    fprintf(stderr, "[kbg reasons] stage planes %d classes x %d words: %.1f us (alloc %.1f, kernel %.1f, download %.1f)\n",
+            S.n_classes, S.W, us(t0, clk::now()), us(t0, t1), us(t1, t2), us(t2, clk::now()));
+  return KBG_OK;
+}
+
 kbg_status fit_deltas_device(Session& S, const std::vector<kbg_decision>& dec, const std::vector<Res>& dec_old,
                              const std::vector<LastEval>& last, const std::vector<int32_t>& jobs) {
+  const bool why = S.opts.reasons && !S.comm;
   std::vector<int32_t> qj;
   int32_t kmin = (int32_t)dec.size();
   for (int32_t j : jobs) {
@@ -382,9 +413,54 @@ kbg_status fit_deltas_device(Session& S, const std::vector<kbg_decision>& dec, c
                  (const int32_t*)(S.fit_d + o_hk), (const double*)(S.fit_d + o_hold), (const int32_t*)(S.fit_d + o_na),
                  (const kbg::FitQuery*)(S.fit_d + o_q), Q, S.pred_active ? 1 : 0, fit_out, S.tab_lo, S.tab_n};
   trace_add("fit.staged", Q);
+  const bool why_prof = why && getenv("KBG_PROFILE_REASONS") != nullptr;
+  if (why_prof) {
+    for (auto& e : S.why_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(S.why_ev[0], S.stream));
+  }
   HIP_TRY(kbg::launch_fitdelta(a, S.stream));
+  if (why) {  // the same staging, in the same launch sequence
+    if (why_prof) HIP_TRY(hipEventRecord(S.why_ev[1], S.stream));
+    const size_t why_bytes = (size_t)Q * kbg::kReasonOut * 4;
+    if (why_bytes > S.why_out_cap) {
+      pool_put(S.why_out);
+      S.why_out = nullptr;
+      S.why_out_cap = 0;
+      if (host_alloc((void**)&S.why_out, why_bytes) != KBG_OK) return fail(KBG_E_HIP, "reasons results");
+      S.why_out_cap = why_bytes;
+    }
+    int32_t* why_out = dev_ptr(S, S.why_out);
+    if (!why_out) return fail(KBG_E_HIP, "hipHostGetDevicePointer of the reasons buffer failed");
+    const kbg::StagePlanes sp = kbg::kbg_stage_planes(S.d_stage, S.n_classes, S.W);
+    kbg::ReasonArgs ra{a.nodes, a.stride, a.W, sp.sel_ok, sp.taint_ok, sp.unsched, sp.live, a.hoff, a.hk, a.q, Q,
+                       a.cap_check, why_out, a.tab_lo, a.tab_n};
+    HIP_TRY(kbg::launch_reasons(ra, S.stream));
+    if (why_prof) HIP_TRY(hipEventRecord(S.why_ev[2], S.stream));
+  }
   HIP_TRY(hipStreamSynchronize(S.stream));
   trace_add("fit.kernel", 0);
+  if (why) {
+    if (why_prof) {
+      float fit_ms = 0, why_ms = 0;
+      HIP_TRY(hipEventElapsedTime(&fit_ms, S.why_ev[0], S.why_ev[1]));
+      HIP_TRY(hipEventElapsedTime(&why_ms, S.why_ev[1], S.why_ev[2]));
+      fprintf(stderr, "[kbg reasons] %d queries x %d nodes: fitdelta kernel %.1f us, reasons kernel %.1f us\n", Q, N,
+              fit_ms * 1e3, why_ms * 1e3);
+    }
+    for (int32_t i = 0; i < Q; ++i) {
+      const int32_t* o = S.why_out + (size_t)kbg::kReasonOut * i;
+      kbg_job_reasons& jr = S.reasons[qj[i]];
+      jr.valid = 1;
+      jr.task = last[qj[i]].task;
+      jr.before = last[qj[i]].before;
+      jr.visited = o[0];
+      for (int k = 0; k < KBG_WHY_COUNT; ++k) {
+        jr.count[k] = o[1 + k];
+        jr.first_node[k] = o[7 + k];
+      }
+    }
+  }
   if (S.svc)  // each rank counted its own nodes
     if (kbg_status st = svc_sum_counts(S, S.fit_out, (size_t)Q * 4); st != KBG_OK) return st;
   for (int32_t i = 0; i < Q; ++i) {
@@ -400,10 +476,14 @@ kbg_status fit_deltas_device(Session& S, const std::vector<kbg_decision>& dec, c
 kbg_status compute_fit_deltas(Session& S, const std::vector<kbg_decision>& dec, const std::vector<Res>& dec_old,
                               const std::vector<uint64_t>& dec_oldp, const std::vector<LastEval>& last) {
   S.fit.assign(S.n_jobs, Session::FitCounts{});
+  const bool why = S.opts.reasons && !S.comm;  // (a communicator's ranks would have to sum theirs: kbg_job_reasons_get)
+  if (why) S.reasons.assign(S.n_jobs, kbg_job_reasons{});
   std::vector<int32_t> jobs;
   for (int32_t j = 0; j < S.n_jobs; ++j)
     if (S.committed_ready[j] < S.job_min[j]) jobs.push_back(j);  // (job_min: jobs_in[j].min_available, compact)
   if (jobs.empty()) return KBG_OK;
+  if (why)
+    if (kbg_status st = ensure_stage_planes(S); st != KBG_OK) return st;
   const bool host_only = getenv("KBG_HOST_FITDELTA") != nullptr;  // read per cycle (A/B parity tests)
   if (S.stream && (!S.comm || S.svc) && !S.has_ports && !S.has_aff && !S.any_nil && !host_only)
     return fit_deltas_device(S, dec, dec_old, last, jobs);
@@ -439,7 +519,43 @@ kbg_status compute_fit_deltas(Session& S, const std::vector<kbg_decision>& dec, 
     const int32_t end = le.node < 0 ? S.n_nodes : le.node + (le.kind == KBG_KIND_PIPELINE ? 1 : 0);
     bool nil_seen = false;
     Res nil_delta{};
+    // the stage that turned each visited live node away, tested in the
+    // reference's order (predicates.go:125-198), which is not the order of the
+    // chain below: the static bit is split with the stage planes
+    kbg_job_reasons* jr = why ? &S.reasons[j] : nullptr;
+    bool nil_visited = false;
+    kbg::StagePlanes sp{};
+    if (jr) {
+      sp = kbg::kbg_stage_planes(S.h_stage.data(), S.n_classes, S.W);
+      jr->valid = 1;
+      jr->task = t;
+      jr->before = le.before;
+      std::fill(jr->first_node, jr->first_node + KBG_WHY_COUNT, -1);
+      // the node an Allocate took passed every stage: visited, and no more
+      if (le.node >= 0 && le.kind != KBG_KIND_PIPELINE && ((sp.live[le.node >> 6] >> (le.node & 63)) & 1ull)) jr->visited++;
+    }
+    auto stage_of = [&](int32_t n) -> int {
+      const size_t w = (size_t)S.task_class[t] * S.W + (n >> 6);
+      const uint64_t bit = 1ull << (n & 63);
+      if (ntasks[n] >= S.maxtasks[n]) return KBG_WHY_POD_CAP;
+      if (!(sp.sel_ok[w] & bit)) return KBG_WHY_SELECTOR;
+      if (conf)
+        for (int32_t pw = 0; pw < PW; ++pw)
+          if (ports[(size_t)n * PW + pw] & conf[pw]) return KBG_WHY_HOST_PORTS;
+      if (sp.unsched[n >> 6] & bit) return KBG_WHY_UNSCHEDULABLE;
+      if (!(sp.taint_ok[w] & bit)) return KBG_WHY_TAINTS;
+      if (S.has_aff && !kbg::aff_ok(S, aff, S.task_class[t], n)) return KBG_WHY_POD_AFFINITY;
+      return -1;
+    };
     for (int32_t n = 0; n < end; ++n) {
+      if (jr && ((sp.live[n >> 6] >> (n & 63)) & 1ull)) {
+        jr->visited++;
+        if (S.panic_node[n]) nil_visited = true;
+        else if (S.pred_active)
+          if (const int c = stage_of(n); c >= 0) {
+            if (jr->count[c]++ == 0) jr->first_node[c] = n;
+          }
+      }
       if (!((cm[n >> 6] >> (n & 63)) & 1ull)) continue;                 // static predicate
       if (S.pred_active && ntasks[n] >= S.maxtasks[n]) continue;       // pod cap
       if (conf && !S.panic_node[n]) {                                  // host ports
@@ -463,6 +579,10 @@ kbg_status compute_fit_deltas(Session& S, const std::vector<kbg_decision>& dec, 
       fc.mem += d.m < 0;
       fc.gpu += d.g < 0;
     }
+    // a nil Node under the predicates plugin inside a visited range: the
+    // reference panicked there (SetNode(nil), predicates.go:122-123), the cycle
+    // did not finish and there is nothing to report for this job
+    if (jr && nil_visited) *jr = kbg_job_reasons{};
     if (nil_seen) {
       fc.nodes++;
       fc.cpu += nil_delta.c < 0;
@@ -484,6 +604,7 @@ void begin_cycle(Session& S) {
   S.committed_ready = S.job_ready0;
   S.fin = S.init;
   S.fit.assign(S.n_jobs, Session::FitCounts{});
+  S.reasons.clear();
   const kbg_stats prev = S.stats;
   S.stats = kbg_stats{};
   S.vk_timed_ms = 0;

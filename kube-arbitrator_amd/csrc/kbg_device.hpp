@@ -303,6 +303,46 @@ struct FitArgs {
   int32_t tab_lo, tab_n;       // the global nodes the table holds (a shard of the scan service: its own)
 };
 hipError_t launch_fitdelta(const FitArgs& a, hipStream_t stream);
+
+// Per-predicate unschedulable reasons (kbg_job_reasons). The static predicate
+// split by stage, one bit per node (kbg_stage_mask_kernel): sel_ok and
+// taint_ok per class, unsched and live per table, every stage evaluated on its
+// own, so for a class that is not `always`
+//   class_mask == sel_ok & taint_ok & ~unsched & live
+// (a nil Node passes every stage, as in kbg_mask_kernel: the host reports it).
+struct StagePlanes {
+  uint64_t* sel_ok;    // [class][W] node selector + required node affinity hold
+  uint64_t* taint_ok;  // [class][W] every NoSchedule / NoExecute taint is tolerated
+  uint64_t* unsched;   // [W] Spec.Unschedulable
+  uint64_t* live;      // [W] the node is in ssn.Nodes (not deleted)
+};
+inline size_t kbg_stage_words(int32_t n_classes, int32_t W) { return (2 * (size_t)n_classes + 2) * (size_t)W; }
+inline StagePlanes kbg_stage_planes(uint64_t* block, int32_t n_classes, int32_t W) {
+  const size_t cw = (size_t)n_classes * W;
+  return StagePlanes{block, block + cw, block + 2 * cw, block + 2 * cw + W};
+}
+hipError_t launch_build_stage_planes(const StaticTables& t, int32_t n_classes, int32_t W, const StagePlanes& p,
+                                     hipStream_t stream);
+// kbg_reasons_kernel: per FitError query (FitArgs' staging: hoff, hk, q) the
+// live nodes of the visited range [0, win + 1) (win < 0: [0, end)) counted by
+// the first failing stage in the reference's order; the nodes at or after
+// `end` (the node an Allocate took) are visited only. out[q][kReasonOut]:
+// visited, count[6], first_node[6] (KBG_WHY_* order; host ports and pod
+// affinity stay 0 / -1 here: such sessions take the host path).
+constexpr int kReasonOut = 16;
+struct ReasonArgs {
+  const double* nodes;  // the final node table block (its pod counts and caps)
+  int32_t stride, W;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const int32_t* hoff;
+  const int32_t* hk;
+  const FitQuery* q;
+  int32_t nq, cap_check;  // cap_check 0 (predicates off): every count 0
+  int32_t* out;           // [nq][kReasonOut] (host-mapped)
+  int32_t tab_lo, tab_n;
+};
+hipError_t launch_reasons(const ReasonArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
+                          hipEvent_t stop = nullptr);
 hipError_t launch_mask_apply(uint64_t* class_mask, const MaskDelta* deltas, int32_t n_deltas, hipStream_t stream);
 
 // One victim scan evaluates every node of the range for one (preemptor,

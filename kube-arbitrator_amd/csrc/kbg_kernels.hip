@@ -15,6 +15,9 @@
 //                     the Allocate/Pipeline kind of each.
 // kbg_mask_kernel   — session-open static predicate masks (class x node bits).
 // kbg_apply_kernel  — NodeInfo.AddTask deltas committed by the host.
+// kbg_stage_mask_kernel, kbg_reasons_kernel — kbg_options.reasons: the static
+//                     predicate split by stage, and per not-ready job the nodes
+//                     counted by the first stage that turned its task away.
 //
 // fp64 is compared with the reference's own expression; the file is compiled
 // with -ffp-contract=off so nothing is fused.
@@ -715,6 +718,115 @@ hipError_t launch_fitdelta(const FitArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ------------------------------------------- unschedulable reasons per stage
+// The predicates plugin returns at its first failing stage (predicates.go:
+// 121-201); this counts, for the task and evaluation point of each FitError
+// query, the live nodes of the visited range by that stage, in the
+// reference's order: pod cap, selector / node affinity, (host ports),
+// unschedulable, taints, (pod affinity) — sessions with host ports or pod
+// affinity take the host path, so those two stay empty here. Same geometry
+// and staging as kbg_fitdelta_kernel: kFitJobs queries per workgroup, a lane
+// per node, 1024 nodes a pass, the node's records loaded once for the group's
+// queries and the stage words (kbg_stage_mask_kernel) the same address across
+// a wave. The pod count at the evaluation point is the final count minus the
+// node's decisions at or after the point (the same binary search); it can
+// only have been at the cap then if it is now, so other nodes skip the
+// search. Per wave: ballots, popcounts and the lowest set bit of the first
+// non-empty ballot per reason (the passes ascend); per workgroup: LDS sums and
+// minima; the results leave as plain stores, nothing crosses workgroups.
+__global__ __launch_bounds__(kFitBlock) void kbg_reasons_kernel(ReasonArgs a) {
+  constexpr int kStages = 4;                 // the stages seen here and their KBG_WHY_* codes
+  constexpr int kCode[kStages] = {0, 1, 3, 4};
+  __shared__ int32_t s_out[kFitJobs][kReasonOut];  // visited, count[6], first_node[6]
+  const int q0 = blockIdx.x * kFitJobs;
+  const int nj = min(kFitJobs, a.nq - q0);
+  if (threadIdx.x < kFitJobs * kReasonOut) {
+    const int k = threadIdx.x % kReasonOut;
+    s_out[threadIdx.x / kReasonOut][k] = k >= 7 && k < 13 ? INT_MAX : 0;
+  }
+  __syncthreads();
+  const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * (size_t)a.stride);
+  const int tab_end = a.tab_lo + a.tab_n;
+  int n_end = 0;  // the furthest visited node of the group's queries
+  for (int jj = 0; jj < nj; ++jj) {
+    const FitQuery& fq = a.q[q0 + jj];
+    n_end = max(n_end, min(fq.win >= 0 ? fq.win + 1 : fq.end, tab_end));
+  }
+  const int last = max(a.tab_lo, n_end - 1);  // a legal node for clamped loads
+  int visited[kFitJobs] = {}, cnt[kFitJobs][kStages] = {}, first[kFitJobs][kStages];
+#pragma unroll
+  for (int jj = 0; jj < kFitJobs; ++jj)
+#pragma unroll
+    for (int s = 0; s < kStages; ++s) first[jj][s] = INT_MAX;
+  for (int base = a.tab_lo; base < n_end; base += kFitBlock) {
+    const int n = base + (int)threadIdx.x;
+    const int nc = min(n, last);
+    const int r = nc - a.tab_lo;
+    const int e0 = a.hoff[nc], e1 = a.hoff[nc + 1], nt = ni[r], mt = ni[a.stride + r];
+    const int wave_n = __builtin_amdgcn_readfirstlane(base + (int)(threadIdx.x & ~63));
+    const uint64_t bit = 1ull << (n & 63);
+    const bool live = (a.live[nc >> 6] & bit) != 0, uns = (a.unsched[nc >> 6] & bit) != 0;
+#pragma unroll
+    for (int jj = 0; jj < kFitJobs; ++jj) {
+      if (jj >= nj) break;
+      const FitQuery& fq = a.q[q0 + jj];
+      const int end = min(fq.end, tab_end);
+      const int vend = min(fq.win >= 0 ? fq.win + 1 : fq.end, tab_end);
+      if (wave_n >= vend) continue;  // the wave is past it
+      const uint64_t so = a.sel_ok[(size_t)fq.cls * a.W + (nc >> 6)], to = a.taint_ok[(size_t)fq.cls * a.W + (nc >> 6)];
+      const bool in = n < vend && live;
+      bool why[kStages] = {};
+      if (in && n < end && a.cap_check) {  // (the node an Allocate took passed every stage)
+        bool capped = false;
+        if (nt >= mt) {
+          int lo = e0, hi = e1;  // the node's first decision at or after the evaluation
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((a.hk[mid] & 0x7fffffff) < fq.point) lo = mid + 1;
+            else hi = mid;
+          }
+          capped = nt - (e1 - lo) >= mt;  // predicates.go:125-127
+        }
+        if (capped) why[0] = true;
+        else if (!(so & bit)) why[1] = true;  // :129-141
+        else if (uns) why[2] = true;          // :157-169
+        else if (!(to & bit)) why[3] = true;  // :171-183
+      }
+      visited[jj] += __popcll(__ballot(in));
+#pragma unroll
+      for (int s = 0; s < kStages; ++s) {
+        const uint64_t b = __ballot(why[s]);
+        cnt[jj][s] += __popcll(b);
+        if (b && first[jj][s] == INT_MAX) first[jj][s] = wave_n + __builtin_ctzll(b);
+      }
+    }
+  }
+  if ((threadIdx.x & 63) == 0)  // (the counts are wave-uniform)
+#pragma unroll
+    for (int jj = 0; jj < kFitJobs; ++jj)
+      if (visited[jj]) {
+        atomicAdd(&s_out[jj][0], visited[jj]);
+#pragma unroll
+        for (int s = 0; s < kStages; ++s)
+          if (cnt[jj][s]) {
+            atomicAdd(&s_out[jj][1 + kCode[s]], cnt[jj][s]);
+            atomicMin(&s_out[jj][7 + kCode[s]], first[jj][s]);
+          }
+      }
+  __syncthreads();
+  if (threadIdx.x < nj * kReasonOut) {
+    const int32_t v = s_out[threadIdx.x / kReasonOut][threadIdx.x % kReasonOut];
+    a.out[kReasonOut * (size_t)q0 + threadIdx.x] = v == INT_MAX ? -1 : v;
+  }
+}
+
+hipError_t launch_reasons(const ReasonArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.nq <= 0) return hipSuccess;
+  hipExtLaunchKernelGGL(kbg_reasons_kernel, dim3((a.nq + kFitJobs - 1) / kFitJobs), dim3(kFitBlock), 0, stream, start,
+                        stop, 0, a);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- select
 // One wave per row walks the row's words [w_lo, w_hi) in global node order
 // (shard slots in rank order = ascending node index), so the candidates come
@@ -1271,6 +1383,60 @@ hipError_t launch_build_class_mask(const StaticTables& t, int32_t n_classes, int
                                    hipStream_t stream) {
   if (n_classes <= 0 || W <= 0) return hipSuccess;
   hipLaunchKernelGGL(kbg_mask_kernel, dim3((W + 3) / 4, n_classes), dim3(256), 0, stream, t, W, class_mask);
+  return hipGetLastError();
+}
+
+// The same programs with every stage kept apart (kbg_job_reasons): the
+// consumer takes the first failing stage in the reference's order, which is
+// not the order above, so nothing short-circuits between stages. Class 0's
+// workgroups also write the two per-table planes.
+__global__ __launch_bounds__(256) void kbg_stage_mask_kernel(StaticTables t, int32_t W, StagePlanes p) {
+  const int lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int cls = blockIdx.y;
+  if (chunk >= W) return;
+  const int node = chunk * 64 + lane;
+  bool sel = false, tol = false, uns = false, live = false;
+  if (node < t.n_nodes) {
+    const ClassProg c = t.classes[cls];
+    const uint8_t fl = t.node_flags[node];
+    const bool nil = (fl & NF_NIL) != 0;  // SetNode(nil) panics before any check: passes every stage here
+    live = nil || !(fl & NF_DEAD);
+    uns = !nil && (fl & NF_UNSCHED);
+    sel = tol = true;
+    if (!c.always && !nil) {
+      if (c.sel_req >= 0) sel = eval_req(t, t.reqs[c.sel_req], node);
+      if (sel && c.has_affinity) {
+        bool any_term = false;
+        for (int i = 0; i < c.term_len && !any_term; ++i) {
+          const TermProg tp = t.terms[c.term_off + i];
+          bool all = true;
+          for (int j = 0; j < tp.req_len && all; ++j) all = eval_req(t, t.reqs[tp.req_off + j], node);
+          any_term = all;
+        }
+        sel = any_term;
+      }
+      for (int w = 0; w < t.taint_words; ++w) {
+        const uint64_t nb = t.taint_bits[(size_t)w * t.n_nodes + node];
+        if (nb & ~t.tol_pool[c.tol_off + w]) { tol = false; break; }
+      }
+    }
+  }
+  const uint64_t ms = __ballot(sel), mt = __ballot(tol), mu = __ballot(uns), ml = __ballot(live);
+  if (lane == 0) {
+    p.sel_ok[(size_t)cls * W + chunk] = ms;
+    p.taint_ok[(size_t)cls * W + chunk] = mt;
+    if (cls == 0) {
+      p.unsched[chunk] = mu;
+      p.live[chunk] = ml;
+    }
+  }
+}
+
+hipError_t launch_build_stage_planes(const StaticTables& t, int32_t n_classes, int32_t W, const StagePlanes& p,
+                                     hipStream_t stream) {
+  if (n_classes <= 0 || W <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kbg_stage_mask_kernel, dim3((W + 3) / 4, n_classes), dim3(256), 0, stream, t, W, p);
   return hipGetLastError();
 }
 

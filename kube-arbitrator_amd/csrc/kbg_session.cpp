@@ -765,6 +765,16 @@ void free_device(Session& S) {
   S.fit_out = nullptr;
   S.fit_d = nullptr;
   S.fit_cap = S.fit_out_cap = 0;
+  pool_put(S.why_out);
+  S.why_out = nullptr;
+  S.why_out_cap = 0;
+  S.d_stage = nullptr;  // (one of d_allocs)
+  S.stage_valid = false;
+  for (auto& e : S.why_ev)
+    if (e) {
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
   if (S.h_vbits) (void)hipHostFree(S.h_vbits);
   if (S.h_vbig) (void)hipHostFree(S.h_vbig);
   S.h_vbig = nullptr;
@@ -1395,6 +1405,20 @@ kbg_status kbg_job_state_get(kbg_session* s, int32_t job, kbg_job_state* out) {
     out->fit_memory = S.fit[job].mem;
     out->fit_gpu = S.fit[job].gpu;
   }
+  return KBG_OK;
+}
+
+kbg_status kbg_job_reasons_get(kbg_session* s, int32_t job, kbg_job_reasons* out) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (!out) return fail(KBG_E_INVALID, "null argument");
+  Session& S = s->s;
+  if (!S.opts.reasons) return fail(KBG_E_INVALID, "the session was opened without kbg_options.reasons");
+  if (S.comm) return fail(KBG_E_UNSUPPORTED, "unschedulable reasons on a session over a communicator");
+  if (job < 0 || job >= S.n_jobs) return fail(KBG_E_INVALID, "job index");
+  *out = kbg_job_reasons{};
+  // the same jobs as FitError: not ready now, evaluated by this cycle's allocate
+  if (S.cycle_started && S.committed_ready[job] < S.jobs_in[job].min_available && (size_t)job < S.reasons.size())
+    *out = S.reasons[job];
   return KBG_OK;
 }
 

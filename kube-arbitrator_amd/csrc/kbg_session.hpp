@@ -477,6 +477,14 @@ struct Session {
   char* fit_d = nullptr;
   int32_t* fit_out = nullptr;
   size_t fit_cap = 0, fit_out_cap = 0;
+  // ---- per-predicate unschedulable reasons (kbg_options.reasons; kbg_job_reasons_get)
+  std::vector<kbg_job_reasons> reasons;     // per job, filled with the FitError counts
+  std::vector<uint64_t> h_stage;            // host copy of the stage planes (kbg::StagePlanes layout)
+  uint64_t* d_stage = nullptr;              // the planes on the device, built at the first cycle that needs them
+  bool stage_valid = false;                 // h_stage (and d_stage, with a device) match the static tables
+  int32_t* why_out = nullptr;               // kbg_reasons_kernel results (mapped)
+  size_t why_out_cap = 0;
+  hipEvent_t why_ev[3] = {nullptr, nullptr, nullptr};  // KBG_PROFILE_REASONS: around the FitError and reasons kernels
   std::vector<uint64_t> h_class_mask;       // host copy of the class masks the scan reads (static predicate,
                                             // and with host ports the dynamic port fit)
   // ---- host ports (vendor predicates.go:1031-1051). A node's used ports only

@@ -144,7 +144,8 @@ class kbg_snapshot(ctypes.Structure):
 
 class kbg_options(ctypes.Structure):
     _fields_ = [("device", i32), ("heap_rule", i32), ("batch_tasks", i32), ("candidates", i32),
-                ("full_scan", i32), ("shards", i32), ("plugin_registry", i32), ("reserved", i32 * 5)]
+                ("full_scan", i32), ("shards", i32), ("plugin_registry", i32), ("reasons", i32),
+                ("reserved", i32 * 4)]
 
 
 class kbg_decision(ctypes.Structure):
@@ -155,6 +156,15 @@ class kbg_job_state(ctypes.Structure):
     _fields_ = [("ready_num", i32), ("ready", i32), ("drf_share", f64), ("drf_allocated", kbg_resource),
                 ("fit_valid", i32), ("fit_nodes", i32), ("fit_cpu", i32), ("fit_memory", i32), ("fit_gpu", i32),
                 ("reserved", i32 * 3)]
+
+
+# kbg_job_reasons.count / first_node indices: the predicates plugin's stages in its order
+WHY_POD_CAP, WHY_SELECTOR, WHY_HOST_PORTS, WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY = range(6)
+
+
+class kbg_job_reasons(ctypes.Structure):
+    _fields_ = [("valid", i32), ("task", i32), ("before", i32), ("visited", i32), ("count", i32 * 6),
+                ("first_node", i32 * 6), ("reserved", i32 * 2)]
 
 
 class kbg_queue_state(ctypes.Structure):
@@ -246,6 +256,7 @@ SIGNATURES = {
     "kbg_apply": (i32, [ctypes.c_void_p, i32, P(kbg_resource), i32]),
     "kbg_job_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_state)]),
     "kbg_queue_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_queue_state)]),
+    "kbg_job_reasons_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_reasons)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -53,6 +53,36 @@ def fit_error(nodes, cpu, memory, gpu):
     return f"0/{nodes} nodes are available, {', '.join(sorted(reasons))}."
 
 
+# The predicates plugin's error per stage (predicates.go:125-198), without the
+# names it formats in, in kbg_job_reasons.count order.
+STAGE_TEXTS = ("can not allow more task running on it", "didn't match node selector",
+               "didn't have available host ports", "set to unschedulable", "does not tolerate node taints",
+               "affinity/anti-affinity failed")
+
+
+def unschedulable_message(reasons, fit=None):
+    """One line, kube-scheduler style, for a job that did not get ready: the
+    nodes its last evaluated task visited by the predicate stage that turned
+    them away (kbg_job_reasons), then FitError's resource parts for the nodes
+    that passed them all (kbg_job_state). Each group is sorted as FitError
+    sorts its own (sort.Strings of the "<n> <text>" parts)."""
+    if not reasons.valid or reasons.visited == 0:
+        return "0 nodes are available"
+    parts = sorted(f"{n} {text}" for n, text in zip(reasons.count, STAGE_TEXTS) if n > 0)
+    if fit is not None and fit.fit_valid:
+        parts += sorted(f"{v} insufficient {k}" for k, v in (("cpu", fit.fit_cpu), ("memory", fit.fit_memory),
+                                                            ("GPU", fit.fit_gpu)) if v > 0)
+    if not parts:
+        return f"0/{reasons.visited} nodes are available."
+    return f"0/{reasons.visited} nodes are available: {', '.join(parts)}."
+
+
+def reasons_row(st):
+    """A kbg_job_reasons as the output rows carry it."""
+    return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),
+            "first_node": list(st.first_node)}
+
+
 def run_fixture(fx, options=None):
     """Returns (result dict in the oracle's output schema, session)."""
     opts = dict(options or {})
@@ -105,6 +135,10 @@ def session_output(ssn, binds, status="ok"):
             row["drf_share"] = st.drf_share
         if st.fit_valid:
             row["fit_error"] = fit_error(st.fit_nodes, st.fit_cpu, st.fit_memory, st.fit_gpu)
+        if getattr(ssn, "reasons", False):  # only sessions opened with reasons: every other output is as before
+            why = ssn.job_reasons(j)
+            if why.valid:
+                row["reasons"] = dict(reasons_row(why), message=unschedulable_message(why, st))
         out["jobs"].append(row)
     for q, queue in enumerate(ssn.queues):
         st = ssn.queue_state(q)

@@ -57,7 +57,7 @@ def _copy_job_fields(src, dst):
 class Session:
     """framework.Session (session.go:35-61) plus the device handle."""
 
-    def __init__(self, cache, tiers, options=None):
+    def __init__(self, cache, tiers, options=None, reasons=False):
         snap = cache.snapshot()
         self.cache = cache
         self.jobs = snap.jobs  # JobValid is a no-op at openSession time (SURVEY F6)
@@ -79,6 +79,10 @@ class Session:
         comm = options.pop("comm", None)  # dist.ShardComm: node-axis shard of an RCCL clique
         for k, v in options.items():
             setattr(opts, k, v)
+        if reasons:
+            opts.reasons = 1
+        # allocate also computes the unschedulable reasons (job_reasons; not over a communicator)
+        self.reasons = bool(opts.reasons) and comm is None
         L = _abi.lib()
         if comm is not None:
             _abi.check(L.kbg_session_open_sharded(ctypes.byref(self.flat.snap), ctypes.byref(opts), comm.handle,
@@ -567,6 +571,14 @@ class Session:
         _abi.check(_abi.lib().kbg_job_state_get(self.handle, j, ctypes.byref(st)))
         return st
 
+    def job_reasons(self, j):
+        """kbg_job_reasons of job j after allocate: the nodes that turned its
+        last evaluated task away, per predicate stage (sessions opened with
+        reasons=True)."""
+        st = _abi.kbg_job_reasons()
+        _abi.check(_abi.lib().kbg_job_reasons_get(self.handle, j, ctypes.byref(st)))
+        return st
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))
@@ -588,8 +600,8 @@ class Session:
             self.handle = ctypes.c_void_p()
 
 
-def open_session(cache, tiers, options=None):
-    return Session(cache, tiers, options)
+def open_session(cache, tiers, options=None, reasons=False):
+    return Session(cache, tiers, options, reasons=reasons)
 
 
 def close_session(ssn):

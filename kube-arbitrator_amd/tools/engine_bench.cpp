@@ -204,6 +204,43 @@ void host_class_mask(Session& S, const kbg::StaticHost& sh) {
   }
 }
 
+// The stage planes of kbg_stage_mask_kernel (kbg_options.reasons) from the
+// same host evaluation: every stage on its own, a nil Node passing them all.
+void host_stage_planes(Session& S, const kbg::StaticHost& sh) {
+  const int32_t N = S.n_nodes;
+  S.h_stage.assign(kbg::kbg_stage_words(S.n_classes, S.W), 0);
+  const kbg::StagePlanes p = kbg::kbg_stage_planes(S.h_stage.data(), S.n_classes, S.W);
+  for (int32_t n = 0; n < N; ++n) {
+    const uint8_t fl = sh.node_flags[n];
+    const uint64_t bit = 1ull << (n & 63);
+    const bool nil = (fl & kbg::NF_NIL) != 0;
+    if (nil || !(fl & kbg::NF_DEAD)) p.live[n >> 6] |= bit;
+    if (!nil && (fl & kbg::NF_UNSCHED)) p.unsched[n >> 6] |= bit;
+    for (int32_t c = 0; c < S.n_classes; ++c) {
+      const kbg::ClassProg& cp = sh.classes[c];
+      bool sel = true, tol = true;
+      if (!cp.always && !nil) {
+        sel = cp.sel_req < 0 || host_req(sh, sh.reqs[cp.sel_req], N, n);
+        if (sel && cp.has_affinity) {
+          bool any_term = false;
+          for (int32_t i = 0; i < cp.term_len && !any_term; ++i) {
+            const kbg::TermProg& tp = sh.terms[cp.term_off + i];
+            bool all = true;
+            for (int32_t j = 0; j < tp.req_len && all; ++j) all = host_req(sh, sh.reqs[tp.req_off + j], N, n);
+            any_term = all;
+          }
+          sel = any_term;
+        }
+        for (int32_t w = 0; tol && w < sh.taint_words; ++w)
+          if (sh.taint_bits[(size_t)w * N + n] & ~sh.tol_pool[cp.tol_off + w]) tol = false;
+      }
+      if (sel) p.sel_ok[(size_t)c * S.W + (n >> 6)] |= bit;
+      if (tol) p.taint_ok[(size_t)c * S.W + (n >> 6)] |= bit;
+    }
+  }
+  S.stage_valid = true;
+}
+
 // Host state of rank `rank` of R (R = 1: the whole table), as build() leaves it
 // minus the device.
 kbg_status host_open(Session& S, const kbg_snapshot* snap, const kbg_options* o, int32_t R, int32_t rank) {
@@ -228,6 +265,7 @@ kbg_status host_open(Session& S, const kbg_snapshot* snap, const kbg_options* o,
     g.h_down = (uint32_t*)std::malloc(down_cap * 4);
   }
   host_class_mask(S, sh);
+  if (S.opts.reasons) host_stage_planes(S, sh);
   S.h_class_mask_static = S.h_class_mask;
   setup_host_ports(S);
   setup_affinity(S);
@@ -394,6 +432,52 @@ extern "C" int32_t kbg_tool_sharded_allocate_rank(const kbg_snapshot* snap, cons
     st = allocate_sharded(S, io, out, cap, n_out);
   }
   tool_stats(S, stats);
+  host_close(S);
+  return -(int32_t)st;
+}
+
+// One allocate cycle without a device and what kbg_job_reasons_get and
+// kbg_job_state_get then answer for every job (the host path of
+// compute_fit_deltas: the stage planes from the host evaluation above, the
+// node loop over the rewound mirror, host ports included; sessions with pod
+// affinity are KBG_E_UNSUPPORTED here as in the entries above).
+// reasons, jobs: one per job; *get_status the status of kbg_job_reasons_get
+// (the same for every job). dims: n_classes, W, predicates active. masks
+// (optional, masks_cap words): the static class masks [class][W], then with
+// kbg_options.reasons the stage planes sel_ok, taint_ok [class][W], unsched,
+// live [W]. Returns minus the status of the open or the cycle. Test
+// infrastructure only (tests/test_reasons_host.py).
+extern "C" int32_t kbg_tool_reasons_host(const kbg_snapshot* snap, const kbg_options* o, kbg_decision* out, int32_t cap,
+                                         int32_t* n_out, kbg_job_reasons* reasons, int32_t* get_status,
+                                         kbg_job_state* jobs, int32_t* dims, uint64_t* masks, int64_t masks_cap) {
+  std::unique_ptr<kbg_session> ks(new kbg_session());
+  Session& S = ks->s;
+  kbg_status st = host_open(S, snap, o, 1, 0);
+  // (the owner-resolve cycle below does not roll the pod-affinity counts back at a cut)
+  if (st == KBG_OK && S.has_aff) st = fail(KBG_E_UNSUPPORTED, "pod affinity: only a device session's cycle carries it");
+  if (st == KBG_OK) {
+    LocalHub hub(1);
+    LocalIO io(hub, 0);
+    st = allocate_sharded(S, io, out, cap, n_out);
+  }
+  if (st == KBG_OK) {
+    *get_status = KBG_OK;
+    for (int32_t j = 0; j < S.n_jobs && st == KBG_OK; ++j) {
+      const kbg_status g = kbg_job_reasons_get(ks.get(), j, &reasons[j]);
+      if (g != KBG_OK) *get_status = g;
+      st = kbg_job_state_get(ks.get(), j, &jobs[j]);
+    }
+    dims[0] = S.n_classes;
+    dims[1] = S.W;
+    dims[2] = S.pred_active ? 1 : 0;
+    const size_t cw = S.h_class_mask_static.size(), sw = S.opts.reasons ? S.h_stage.size() : 0;
+    if (masks && (int64_t)(cw + sw) <= masks_cap) {
+      std::copy(S.h_class_mask_static.begin(), S.h_class_mask_static.end(), masks);
+      std::copy(S.h_stage.begin(), S.h_stage.begin() + sw, masks + cw);
+    } else if (masks) {
+      st = fail(KBG_E_CAPACITY, "mask buffer too small");
+    }
+  }
   host_close(S);
   return -(int32_t)st;
 }

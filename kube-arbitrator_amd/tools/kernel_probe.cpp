@@ -374,3 +374,128 @@ extern "C" int32_t kbg_tool_probe_apply(int32_t stride, void* nodes, const kbg::
   PROBE_TRY(hipMemcpy(copy_out, d_copy, bytes + kProbeGuardBytes, hipMemcpyDeviceToHost));
   return 0;
 }
+
+struct kbg_probe_stage {
+  int32_t n_nodes, W, classes, label_words, taint_words, n_numcols, n_reqs, n_terms, mask_pool_words, tol_pool_words;
+};
+
+// kbg_stage_mask_kernel, and kbg_mask_kernel on the same tables. label_bits
+// [label_words][n_nodes], taint_bits [taint_words][n_nodes], num_vals, num_ok
+// [n_numcols][n_nodes], name_id, node_flags [n_nodes], the pools, reqs
+// [n_reqs], terms [n_terms], progs [classes]. planes_out: sel_ok, taint_ok
+// [classes][W], unsched, live [W] (kbg_stage_planes) + guard; mask_out:
+// [classes][W] + guard.
+extern "C" int32_t kbg_tool_probe_stage_mask(const kbg_probe_stage* p, const uint64_t* label_bits,
+                                             const uint64_t* taint_bits, const int64_t* num_vals, const uint8_t* num_ok,
+                                             const int32_t* name_id, const uint8_t* node_flags,
+                                             const uint64_t* mask_pool, const uint64_t* tol_pool,
+                                             const kbg::ReqProg* reqs, const kbg::TermProg* terms,
+                                             const kbg::ClassProg* progs, void* planes_out, void* mask_out) {
+  t_error.clear();
+  if (!p || !label_bits || !taint_bits || !num_vals || !num_ok || !name_id || !node_flags || !mask_pool || !tol_pool ||
+      !reqs || !terms || !progs || !planes_out || !mask_out)
+    return reject("null argument");
+  if (p->classes < 1 || p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->label_words < 0 || p->taint_words < 0 || p->n_numcols < 0 || p->n_reqs < 0 || p->n_terms < 0)
+    return reject("negative count");
+  for (int32_t i = 0; i < p->n_reqs; ++i) {
+    const kbg::ReqProg& r = reqs[i];
+    if (r.kind < kbg::REQ_FALSE || r.kind > kbg::REQ_NAME_NE) return reject("requirement kind");
+    if (r.kind >= kbg::REQ_ALL && r.kind <= kbg::REQ_NONE &&
+        (r.mask_off < 0 || r.mask_off + p->label_words > p->mask_pool_words))
+      return reject("requirement mask outside the pool");
+    if ((r.kind == kbg::REQ_GT || r.kind == kbg::REQ_LT) && (r.col < 0 || r.col >= p->n_numcols))
+      return reject("requirement column");
+  }
+  for (int32_t i = 0; i < p->n_terms; ++i)
+    if (terms[i].req_off < 0 || terms[i].req_len < 0 || terms[i].req_off + terms[i].req_len > p->n_reqs)
+      return reject("term outside the requirements");
+  for (int32_t c = 0; c < p->classes; ++c) {
+    const kbg::ClassProg& k = progs[c];
+    if (k.sel_req >= p->n_reqs) return reject("class selector outside the requirements");
+    if (k.has_affinity && (k.term_off < 0 || k.term_len < 0 || k.term_off + k.term_len > p->n_terms))
+      return reject("class terms outside the terms");
+    if (k.tol_off < 0 || k.tol_off + p->taint_words > p->tol_pool_words) return reject("class tolerations outside the pool");
+  }
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t N = (size_t)p->n_nodes;
+  kbg::StaticTables t{};
+  t.n_nodes = p->n_nodes;
+  t.label_words = p->label_words;
+  t.taint_words = p->taint_words;
+  t.n_numcols = p->n_numcols;
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.label_bits, label_bits, (size_t)p->label_words * N));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.taint_bits, taint_bits, (size_t)p->taint_words * N));
+  PROBE_TRY(dev_copy(sc, (int64_t**)&t.num_vals, num_vals, (size_t)p->n_numcols * N));
+  PROBE_TRY(dev_copy(sc, (uint8_t**)&t.num_ok, num_ok, (size_t)p->n_numcols * N));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.name_id, name_id, N));
+  PROBE_TRY(dev_copy(sc, (uint8_t**)&t.node_flags, node_flags, N));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.mask_pool, mask_pool, (size_t)p->mask_pool_words));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.tol_pool, tol_pool, (size_t)p->tol_pool_words));
+  PROBE_TRY(dev_copy(sc, (kbg::ReqProg**)&t.reqs, reqs, (size_t)p->n_reqs));
+  PROBE_TRY(dev_copy(sc, (kbg::TermProg**)&t.terms, terms, (size_t)p->n_terms));
+  PROBE_TRY(dev_copy(sc, (kbg::ClassProg**)&t.classes, progs, (size_t)p->classes));
+  const size_t plane_bytes = kbg::kbg_stage_words(p->classes, p->W) * 8 + kProbeGuardBytes;
+  const size_t mask_bytes = (size_t)p->classes * p->W * 8 + kProbeGuardBytes;
+  char *d_planes = nullptr, *d_mask = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_planes, (const char*)nullptr, plane_bytes, kProbeSentinel));
+  PROBE_TRY(dev_copy(sc, &d_mask, (const char*)nullptr, mask_bytes, kProbeSentinel));
+  PROBE_TRY(kbg::launch_build_stage_planes(t, p->classes, p->W, kbg::kbg_stage_planes((uint64_t*)d_planes, p->classes, p->W),
+                                           sc.stream));
+  PROBE_TRY(kbg::launch_build_class_mask(t, p->classes, p->W, (uint64_t*)d_mask, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(planes_out, d_planes, plane_bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(mask_out, d_mask, mask_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// kbg_reasons_kernel on kbg_fitdelta_kernel's staging (kbg_probe_fit; hold and
+// na are not read). planes: sel_ok, taint_ok [classes][W], unsched, live [W].
+// out: nq * kReasonOut words + guard (host-mapped).
+extern "C" int32_t kbg_tool_probe_reasons(const kbg_probe_fit* p, const void* nodes, const uint64_t* planes,
+                                          const int32_t* hoff, const int32_t* hk, const kbg::FitQuery* q, void* out) {
+  t_error.clear();
+  if (!p || !nodes || !planes || !hoff || !hk || !q || !out) return reject("null argument");
+  if (p->nq < 1 || p->classes < 1) return reject("empty launch");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (!table_ok(p->stride, p->tab_lo, p->tab_n) || p->tab_lo + p->tab_n > p->n_nodes)
+    return reject("window rows outside the table block");
+  if (hoff[0] != 0 || hoff[p->n_nodes] != p->n_dec) return reject("hoff does not span the decisions");
+  for (int32_t n = 0; n < p->n_nodes; ++n)
+    if (hoff[n + 1] < hoff[n]) return reject("hoff not increasing");
+  for (int32_t i = 0; i < p->nq; ++i)
+    if (q[i].cls < 0 || q[i].cls >= p->classes || q[i].end < 0 || q[i].end > p->n_nodes || q[i].win < -1 ||
+        q[i].win >= p->n_nodes)
+      return reject("query outside the planes");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  kbg::ReasonArgs a{};
+  uint64_t* d_planes = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&a.nodes, (const char*)nodes, (size_t)p->stride * 56));
+  PROBE_TRY(dev_copy(sc, &d_planes, planes, kbg::kbg_stage_words(p->classes, p->W)));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.hoff, hoff, (size_t)p->n_nodes + 1));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.hk, hk, (size_t)p->n_dec));
+  PROBE_TRY(dev_copy(sc, (kbg::FitQuery**)&a.q, q, (size_t)p->nq));
+  const kbg::StagePlanes sp = kbg::kbg_stage_planes(d_planes, p->classes, p->W);
+  a.sel_ok = sp.sel_ok;
+  a.taint_ok = sp.taint_ok;
+  a.unsched = sp.unsched;
+  a.live = sp.live;
+  a.stride = p->stride;
+  a.W = p->W;
+  a.nq = p->nq;
+  a.cap_check = p->cap_check;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  const size_t out_bytes = (size_t)p->nq * kbg::kReasonOut * 4 + kProbeGuardBytes;
+  char* h_out = nullptr;
+  PROBE_TRY(mapped(sc, &h_out, (char**)&a.out, out_bytes));
+  memset(h_out, kProbeSentinel, out_bytes);
+  PROBE_TRY(kbg::launch_reasons(a, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  memcpy(out, h_out, out_bytes);
+  return 0;
+}
