@@ -3,7 +3,9 @@
 // kbg_device.hpp (or a short chain of them) on a stream of its own,
 // synchronises, copies the outputs back and frees everything. There is no
 // session and no Grouper: tests/test_kernels_gpu.py builds the inputs and
-// compares the raw device output with a plain reference (tests/kernel_ref.py).
+// compares the raw device output with a plain reference (tests/kernel_ref.py);
+// tests/test_victim_kernels_gpu.py does so for the victim scan
+// (tests/victim_ref.py).
 //
 // Output buffers are filled with kProbeSentinel bytes before the launch and
 // are followed by a guard region of kProbeGuardBytes of the same pattern; the
@@ -497,5 +499,176 @@ extern "C" int32_t kbg_tool_probe_reasons(const kbg_probe_fit* p, const void* no
   PROBE_TRY(kbg::launch_reasons(a, sc.stream));
   PROBE_TRY(hipStreamSynchronize(sc.stream));
   memcpy(out, h_out, out_bytes);
+  return 0;
+}
+
+// The scalar fields of VictimScan (the deciding tier's fns in tier_fns, as the
+// session passes one tier at most), then the probe's own.
+struct kbg_probe_victim {
+  int32_t n_nodes, W, cls, cap_check, node_lo, node_n, mode, n_tiers, tier_fns, job, queue;
+  int32_t stride;    // rows of the node table block (row = node - node_lo)
+  int32_t classes;   // rows of class_mask
+  int32_t n_cand, n_jobs, n_queues;
+  int32_t prep;      // 0 none, 1 launch_victim_prep_inline, 2 launch_victim_prep (host-mapped deltas)
+  int32_t nn, ns;    // node deltas, state deltas
+  int32_t out_mode;  // 0 mapped (host-mapped words, row_out bytes), 1 device (device words, atomicOr)
+  int32_t n_rows;    // the caller's count of big rows (sizes row_out); checked against the probe's own
+};
+
+// What try_task runs for one preemptor: an optional prep, kbg_victim_kernel,
+// then kbg_victim_big_kernel over the rows of [node_lo, node_lo + node_n)
+// holding 129..kMaxNodeCandidates candidates (vt_setup's rule). nodes: the
+// table block (stride * 56 bytes), updated in place by the prep, as are c_run
+// [n_cand], j_ready [n_jobs], j_alloc [n_jobs][3], q_alloc [n_queues][3].
+// dbl: req[3], ls, drf_total[3]. stop, panic: kbg_victim_words(n_nodes) words
+// + guard each, in and out (the caller supplies their initial content);
+// row_out: n_rows bytes + guard, written in mapped mode only.
+extern "C" int32_t kbg_tool_probe_victim(const kbg_probe_victim* p, void* nodes, const uint8_t* panic_node,
+                                         const uint64_t* class_mask, const int32_t* nt_off, const int32_t* c_jq,
+                                         const double* c_req, uint8_t* c_run, const int32_t* j_min, int32_t* j_ready,
+                                         double* j_alloc, double* q_alloc, const double* q_deserved, const double* dbl,
+                                         const kbg::NodeDelta* nd, const kbg::StateDelta* sd, void* stop, void* panic,
+                                         void* row_out) {
+  t_error.clear();
+  if (!p || !nodes || !panic_node || !class_mask || !nt_off || !c_jq || !c_req || !c_run || !j_min || !j_ready ||
+      !j_alloc || !q_alloc || !q_deserved || !dbl || !nd || !sd || !stop || !panic || !row_out)
+    return reject("null argument");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->node_lo < 0 || (p->node_lo & 63)) return reject("node_lo not a multiple of 64");
+  if (p->node_n < 1 || (int64_t)p->node_lo + p->node_n > p->n_nodes) return reject("node range outside n_nodes");
+  if (p->stride < 1 || p->node_n > p->stride) return reject("node range outside the table block");
+  if (p->classes < 1 || p->cls < 0 || p->cls >= p->classes) return reject("cls outside class_mask");
+  if (p->mode < kbg::VM_PREEMPT_JOBS || p->mode > kbg::VM_RECLAIM) return reject("mode outside 0..2");
+  if (p->n_tiers < 0 || p->n_tiers > 1) return reject("n_tiers outside {0, 1}");
+  if (p->tier_fns & ~(kbg::VP_GANG | kbg::VP_DRF | kbg::VP_PROP)) return reject("tier_fns outside the victim fns");
+  if (p->n_tiers == 1 && p->tier_fns == 0) return reject("tier_fns: a tier without a victim fn");
+  if (p->n_cand < 0 || p->n_jobs < 1 || p->n_queues < 1) return reject("empty tables");
+  if (p->job < 0 || p->job >= p->n_jobs || p->queue < 0 || p->queue >= p->n_queues)
+    return reject("preemptor job or queue outside its table");
+  if (nt_off[0] != 0 || nt_off[p->n_nodes] != p->n_cand) return reject("nt_off does not span the candidates");
+  for (int32_t n = 0; n < p->n_nodes; ++n)
+    if (nt_off[n + 1] < nt_off[n]) return reject("nt_off not increasing");
+  for (int32_t k = 0; k < p->n_cand; ++k)
+    if (c_jq[2 * k] < 0 || c_jq[2 * k] >= p->n_jobs || c_jq[2 * k + 1] < 0 || c_jq[2 * k + 1] >= p->n_queues)
+      return reject("candidate job or queue outside its table");
+  if (p->prep < 0 || p->prep > 2 || p->nn < 0 || p->ns < 0) return reject("prep outside 0..2");
+  if (p->prep == 0 && p->nn + p->ns != 0) return reject("prep: deltas without a prep launch");
+  if (p->prep == 1 && (p->nn > kbg::kArgNodeDeltas || p->ns > kbg::kArgStateDeltas))
+    return reject("prep: more deltas than the inline arguments hold");
+  if (p->ns > kbg::kMaskDeltaCap) return reject("prep: more state deltas than one staging holds");
+  {
+    std::vector<char> seen_row(p->stride, 0);
+    for (int32_t i = 0; i < p->nn; ++i) {
+      if (nd[i].node < 0 || nd[i].node >= p->stride) return reject("delta: node row outside the table block");
+      if (seen_row[nd[i].node]++) return reject("delta: duplicate node row");
+    }
+    const int32_t sizes[4] = {p->n_cand, p->n_jobs, p->n_jobs, p->n_queues};
+    std::vector<char> seen[4];
+    for (int k = 0; k < 4; ++k) seen[k].assign(std::max(sizes[k], 1), 0);
+    for (int32_t i = 0; i < p->ns; ++i) {
+      if (sd[i].kind < 0 || sd[i].kind > 3) return reject("delta: kind outside 0..3");
+      if (sd[i].index < 0 || sd[i].index >= sizes[sd[i].kind]) return reject("delta: index outside its table");
+      if (seen[sd[i].kind][sd[i].index]++) return reject("delta: duplicate (kind, index)");
+    }
+  }
+  // nodes of the range for kbg_victim_big_kernel, as vt_setup lists them
+  std::vector<int32_t> big_rows;
+  for (int32_t n = p->node_lo; n < p->node_lo + p->node_n; ++n) {
+    const int32_t L = nt_off[n + 1] - nt_off[n];
+    if (L > 128 && L <= kbg::kMaxNodeCandidates) big_rows.push_back(n - p->node_lo);
+  }
+  if (p->n_rows != (int32_t)big_rows.size()) return reject("n_rows is not the number of big rows");
+  if (p->out_mode < 0 || p->out_mode > 1) return reject("out_mode outside 0..1");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)p->stride, P = (size_t)p->n_cand, J = (size_t)p->n_jobs, Q = (size_t)p->n_queues;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  const kbg::NodeSoA soa{d, d + L, d + 2 * L, d + 3 * L, d + 4 * L, d + 5 * L, (int32_t*)(d + 6 * L),
+                         (int32_t*)(d + 6 * L) + L};
+  kbg::VictimTables t{};
+  t.ntasks = soa.ntasks;
+  t.maxtasks = soa.maxtasks;
+  PROBE_TRY(dev_copy(sc, (uint8_t**)&t.panic_node, panic_node, (size_t)p->n_nodes));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.class_mask, class_mask, (size_t)p->classes * p->W));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.nt_off, nt_off, (size_t)p->n_nodes + 1));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.c_jq, c_jq, 2 * P));
+  PROBE_TRY(dev_copy(sc, (double**)&t.c_req, c_req, 3 * P));
+  PROBE_TRY(dev_copy(sc, &t.c_run, (const uint8_t*)c_run, P));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.j_queue, (const int32_t*)nullptr, J));  // not read by the kernels
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.j_min, j_min, J));
+  PROBE_TRY(dev_copy(sc, &t.j_ready, (const int32_t*)j_ready, J));
+  PROBE_TRY(dev_copy(sc, &t.j_alloc, (const double*)j_alloc, 3 * J));
+  PROBE_TRY(dev_copy(sc, &t.q_alloc, (const double*)q_alloc, 3 * Q));
+  PROBE_TRY(dev_copy(sc, (double**)&t.q_deserved, q_deserved, 3 * Q));
+  std::copy(dbl + 4, dbl + 7, t.drf_total);
+  int32_t* d_rows = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_rows, big_rows.data(), big_rows.size()));
+
+  kbg::VictimScan a{};
+  a.n_nodes = p->n_nodes;
+  a.W = p->W;
+  a.cls = p->cls;
+  a.cap_check = p->cap_check;
+  a.node_lo = p->node_lo;
+  a.node_n = p->node_n;
+  a.mode = p->mode;
+  a.n_tiers = p->n_tiers;
+  a.tier_fns[0] = p->tier_fns;
+  a.job = p->job;
+  a.queue = p->queue;
+  std::copy(dbl, dbl + 3, a.req);
+  a.ls = dbl[3];
+
+  const size_t word_bytes = (size_t)kbg::kbg_victim_words(p->n_nodes) * 4 + kProbeGuardBytes;
+  const size_t row_bytes = big_rows.size() + kProbeGuardBytes;
+  char *h_stop = nullptr, *h_panic = nullptr, *h_rows = nullptr;
+  uint32_t *d_stop = nullptr, *d_panic = nullptr;
+  uint8_t* d_row_out = nullptr;
+  if (p->out_mode == 0) {
+    PROBE_TRY(mapped(sc, &h_stop, (char**)&d_stop, word_bytes));
+    PROBE_TRY(mapped(sc, &h_panic, (char**)&d_panic, word_bytes));
+    PROBE_TRY(mapped(sc, &h_rows, (char**)&d_row_out, row_bytes));
+    memcpy(h_stop, stop, word_bytes);
+    memcpy(h_panic, panic, word_bytes);
+    memset(h_rows, kProbeSentinel, row_bytes);
+  } else {
+    PROBE_TRY(dev_copy(sc, (char**)&d_stop, (const char*)stop, word_bytes));
+    PROBE_TRY(dev_copy(sc, (char**)&d_panic, (const char*)panic, word_bytes));
+  }
+
+  if (p->prep == 1) {
+    kbg::VictimPrepArgs pa{};
+    pa.nn = p->nn;
+    pa.ns = p->ns;
+    std::copy(nd, nd + p->nn, pa.nd);
+    std::copy(sd, sd + p->ns, pa.sd);
+    PROBE_TRY(kbg::launch_victim_prep_inline(soa, t, pa, sc.stream));
+  } else if (p->prep == 2) {  // read in place from host-mapped memory, as the session's staging is
+    kbg::NodeDelta *h_nd = nullptr, *d_nd = nullptr;
+    kbg::StateDelta *h_sd = nullptr, *d_sd = nullptr;
+    PROBE_TRY(mapped(sc, &h_nd, &d_nd, (size_t)p->nn * sizeof(kbg::NodeDelta)));
+    PROBE_TRY(mapped(sc, &h_sd, &d_sd, (size_t)p->ns * sizeof(kbg::StateDelta)));
+    std::copy(nd, nd + p->nn, h_nd);
+    std::copy(sd, sd + p->ns, h_sd);
+    PROBE_TRY(kbg::launch_victim_prep(soa, t, d_nd, p->nn, d_sd, p->ns, sc.stream));
+  }
+  PROBE_TRY(kbg::launch_victim_scan(a, t, d_stop, d_panic, sc.stream));
+  PROBE_TRY(kbg::launch_victim_big(a, t, d_rows, (int32_t)big_rows.size(), d_stop, d_panic, d_row_out, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  if (p->out_mode == 0) {
+    memcpy(stop, h_stop, word_bytes);
+    memcpy(panic, h_panic, word_bytes);
+    memcpy(row_out, h_rows, row_bytes);
+  } else {
+    PROBE_TRY(hipMemcpy(stop, d_stop, word_bytes, hipMemcpyDeviceToHost));
+    PROBE_TRY(hipMemcpy(panic, d_panic, word_bytes, hipMemcpyDeviceToHost));
+  }
+  PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(c_run, t.c_run, P, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(j_ready, t.j_ready, J * 4, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(j_alloc, t.j_alloc, 3 * J * 8, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(q_alloc, t.q_alloc, 3 * Q * 8, hipMemcpyDeviceToHost));
   return 0;
 }
