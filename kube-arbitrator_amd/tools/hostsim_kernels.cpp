@@ -1,0 +1,438 @@
+// hostsim (developer tool, never shipped): every kbg::launch_* the allocate /
+// backfill / update paths reach, as plain C++ on the simulated stream of
+// hostsim_hip.cpp. Each is the contract of csrc/kbg_device.hpp restated per
+// node and per row — nothing of the kernels' waves, LDS or rounds — and
+// writes exactly the bytes the kernel writes. A launcher copies its argument
+// struct when it is called, as a kernel launch does; memory the arguments
+// point to is read when the operation runs. tests/test_hostsim_kernels.py
+// holds them to the reference the GPU kernels are held to.
+//
+// The four victim launchers are not restated: they answer
+// hipErrorNotSupported, so preempt / reclaim sessions fail cleanly.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../csrc/kbg_device.hpp"
+#include "hostsim.hpp"
+
+namespace kbg {
+namespace {
+
+inline bool le(double r, double a, double mn) { return r < a || std::fabs(a - r) < mn; }  // resource_info.go:142-146
+
+// Resreq.LessEqual(a) for a row's request q (TaskRec: thresholds req - min in integer mode)
+inline bool fits(bool int_mode, const double* q, double a0, double a1, double a2) {
+  if (int_mode) return a0 > q[0] && a1 > q[1] && a2 > q[2];
+  return le(q[0], a0, kMinMilliCPU) && le(q[1], a1, kMinMemory) && le(q[2], a2, kMinMilliGPU);
+}
+
+// The node table as one block (FirstFitArgs.nodes) or as NodeSoA pointers.
+struct Table {
+  const double *ic, *im, *ig, *rc, *rm, *rg;
+  const int32_t *nt, *mt;
+};
+Table table_of(const double* nodes, int32_t stride) {
+  const size_t L = (size_t)stride;
+  const int32_t* i = reinterpret_cast<const int32_t*>(nodes + 6 * L);
+  return Table{nodes, nodes + L, nodes + 2 * L, nodes + 3 * L, nodes + 4 * L, nodes + 5 * L, i, i + L};
+}
+Table table_of(const NodeSoA& n) {
+  return Table{n.idle_cpu, n.idle_mem, n.idle_gpu, n.rel_cpu, n.rel_mem, n.rel_gpu, n.ntasks, n.maxtasks};
+}
+
+// One evaluation row against the 64 nodes of global word w: {fits Idle or
+// Releasing, fits Idle}, static predicate and pod cap applied. Rows of the
+// table are node - tab_lo, nodes outside [tab_lo, tab_lo + tab_n) (tab_n < 0:
+// no upper bound) or at / past n_nodes never fit. On a node whose Releasing
+// is zero the Releasing fit is the row's kRowRelZeroFits flag.
+MaskPair eval_word(const Table& t, const TaskRec& tr, uint64_t static_mask, int32_t w, int32_t n_nodes, int32_t tab_lo,
+                   int32_t tab_n, bool cap_check, bool int_mode) {
+  MaskPair m{0ull, 0ull};
+  for (int b = 0; b < 64; ++b) {
+    const int64_t node = (int64_t)w * 64 + b, row = node - tab_lo;
+    if (node >= n_nodes || row < 0 || (tab_n >= 0 && row >= tab_n)) continue;
+    if (!((static_mask >> b) & 1ull)) continue;
+    if (cap_check && !(t.nt[row] < t.mt[row])) continue;  // predicates.go:125-127
+    const bool fi = fits(int_mode, tr.req, t.ic[row], t.im[row], t.ig[row]);
+    const bool rel_zero = t.rc[row] == 0.0 && t.rm[row] == 0.0 && t.rg[row] == 0.0;
+    const bool fr = rel_zero ? (tr.flags & kRowRelZeroFits) != 0 : fits(int_mode, tr.req, t.rc[row], t.rm[row], t.rg[row]);
+    if (fi) m.i |= 1ull << b;
+    if (fi || fr) m.f |= 1ull << b;
+  }
+  return m;
+}
+
+void firstfit_run(const FirstFitArgs& a, bool int_mode) {
+  const Table t = table_of(a.nodes, a.stride);
+  // the writer row of each shape, if it has one
+  std::vector<char> writer(a.n_shapes, 0);
+  if (a.runs) {
+    std::fill(writer.begin(), writer.end(), 1);
+  } else {
+    for (int32_t g = 0; g < a.G; ++g) {
+      const uint32_t m = a.row_shape ? a.row_shape[g] : ((uint32_t)g | kRowWriter);
+      if (m & kRowWriter) writer[m & ~kRowWriter] = 1;
+    }
+  }
+  for (int32_t s = 0; s < a.n_shapes; ++s) {
+    if (!writer[s]) continue;
+    const TaskRec tr = a.shapes ? a.shapes[s] : a.inl[s];
+    const uint32_t want = a.complete ? 0xffffffffu : ((uint32_t)tr.flags >> kRowWantShift);
+    for (int32_t part = 0; part < a.splits; ++part) {
+      const int32_t lo = a.w_lo + part * a.split_words, hi = std::min(a.w_hi, lo + a.split_words);
+      uint32_t* info = a.info + (size_t)s * a.info_stride + a.part0 + part;
+      const int32_t tw = hi - lo;
+      if (tw <= 0) {  // no words (a session without nodes)
+        *info = 0u;
+        if (a.avail) a.avail[s] = 0u;
+        continue;
+      }
+      // the list ends after the word holding its want-th fit; every covered word's masks go out
+      MaskPair* out = a.masks + (size_t)s * a.mw - a.mask_w0;
+      uint32_t found = 0, covered = 0;
+      bool any = false;
+      for (int32_t w = lo; w < hi; ++w) {
+        // a list that needs nothing (want 0) stays empty; whether a node fits is then
+        // reported from the part's first 64 words only
+        if (found >= want && !(want == 0 && w - lo < 64)) break;
+        const MaskPair m = eval_word(t, tr, a.class_mask[(size_t)tr.cls * a.W + w], w, a.n_nodes, a.tab_lo, a.tab_n,
+                                     a.cap_check != 0, int_mode);
+        any |= m.f != 0ull;
+        if (want == 0) continue;
+        out[w] = m;
+        covered++;
+        found += (uint32_t)__builtin_popcountll(m.f);
+      }
+      *info = covered | (covered < (uint32_t)tw ? kCountIncompleteBit : 0u) | (any ? kInfoAnyBit : 0u);
+      if (a.avail) a.avail[s] = any ? a.avail_bit : 0u;
+    }
+  }
+}
+
+void scan_run(const NodeSoA& n, const ScanGeom& g, const uint64_t* class_mask, const TaskRec* tasks, int32_t n_tasks,
+              bool cap_check, bool int_mode, uint64_t* out) {
+  const Table t = table_of(n);
+  const size_t plane = (size_t)n_tasks * kbg_slot_words(g.Wl);
+  for (int32_t rel = 0; rel < g.n_chunks; ++rel) {
+    const int32_t chunk = g.chunk_lo + rel;
+    if (chunk >= g.W) break;  // words past W are never read or written
+    const int32_t slot = rel / g.Wl, w = rel - slot * g.Wl;
+    for (int32_t r = 0; r < n_tasks; ++r) {
+      const MaskPair m = eval_word(t, tasks[r], class_mask[(size_t)tasks[r].cls * g.W + chunk], chunk, g.n_nodes,
+                                   g.tab_lo, -1, cap_check, int_mode);
+      uint64_t* o = out + (size_t)slot * 2 * plane + ((size_t)(w >> 2) * n_tasks + r) * 4 + (w & 3);
+      o[0] = m.f;
+      o[plane] = m.i;
+    }
+  }
+}
+
+// Per row the first M fits of the words [w_lo, w_hi) in node order. The words
+// are taken 64 at a time and the walk ends after the group in which the list
+// filled, so a list that filled before the last group counts as incomplete
+// whether or not a later word holds a fit.
+void select_run(const uint64_t* bits, int32_t w_lo, int32_t w_hi, int32_t Wl, int32_t n_rows, const uint32_t* cap_off,
+                uint32_t* out_cand, uint32_t* out_count) {
+  const size_t plane = (size_t)n_rows * kbg_slot_words(Wl);
+  for (int32_t r = 0; r < n_rows; ++r) {
+    const int64_t M = (int64_t)cap_off[r + 1] - cap_off[r];
+    uint32_t* cand = out_cand + cap_off[r];
+    int64_t found = 0;
+    int32_t base = w_lo;
+    for (; base < w_hi && found < M; base += 64)
+      for (int32_t c = base; c < std::min(w_hi, base + 64); ++c) {
+        const int32_t slot = c / Wl, w = c - slot * Wl;
+        const uint64_t* p = bits + (size_t)slot * 2 * plane + ((size_t)(w >> 2) * n_rows + r) * 4 + (w & 3);
+        const uint64_t iw = p[plane];
+        for (uint64_t f = p[0]; f; f &= f - 1ull) {
+          const int b = __builtin_ctzll(f);
+          if (found < M) cand[found] = (uint32_t)(c * 64 + b) | (((iw >> b) & 1ull) ? 0u : kCandPipelineBit);
+          ++found;
+        }
+      }
+    const bool complete = base >= w_hi && found <= M;
+    out_count[r] = (uint32_t)std::min(found, M) | (complete ? 0u : kCountIncompleteBit);
+  }
+}
+
+// The node's first decision at or after `point` (its decisions are in log order).
+inline int32_t first_undone(const int32_t* hk, int32_t e0, int32_t e1, int32_t point) {
+  int32_t lo = e0;
+  while (lo < e1 && (hk[lo] & 0x7fffffff) < point) ++lo;
+  return lo;
+}
+
+void fitdelta_run(const FitArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  for (int32_t qi = 0; qi < a.nq; ++qi) {
+    const FitQuery fq = a.q[qi];
+    int32_t cnt[4] = {0, 0, 0, 0};
+    const int32_t end = std::min(fq.end, a.tab_lo + a.tab_n);
+    for (int32_t n = a.tab_lo; n < end; ++n) {
+      if (!((a.class_mask[(size_t)fq.cls * a.W + (n >> 6)] >> (n & 63)) & 1ull)) continue;  // static predicate
+      const int32_t r = n - a.tab_lo, e1 = a.hoff[n + 1];
+      const int32_t lo = first_undone(a.hk, a.hoff[n], e1, fq.point);
+      double c = t.ic[r], m = t.im[r], g = t.ig[r];
+      const int32_t x = lo < e1 ? a.na[lo] : -1;  // the first undone Allocate: Idle before it
+      if (x >= 0) {
+        c = a.hold[3 * (size_t)x];
+        m = a.hold[3 * (size_t)x + 1];
+        g = a.hold[3 * (size_t)x + 2];
+      }
+      const bool capped = a.cap_check && t.nt[r] - (e1 - lo) >= t.mt[r];  // pod cap then
+      const bool chosen =
+          n != fq.win && le(fq.req[0], c, kMinMilliCPU) && le(fq.req[1], m, kMinMemory) && le(fq.req[2], g, kMinMilliGPU);
+      if (capped || chosen) continue;
+      cnt[0]++;  // Resource.FitDelta (resource_info.go:116-129)
+      cnt[1] += (fq.req[0] > 0 ? c - (fq.req[0] + kMinMilliCPU) : c) < 0;
+      cnt[2] += (fq.req[1] > 0 ? m - (fq.req[1] + kMinMemory) : m) < 0;
+      cnt[3] += (fq.req[2] > 0 ? g - (fq.req[2] + kMinMilliGPU) : g) < 0;
+    }
+    for (int k = 0; k < 4; ++k) a.out[4 * (size_t)qi + k] = cnt[k];
+  }
+}
+
+void reasons_run(const ReasonArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  constexpr int kCode[4] = {0, 1, 3, 4};  // KBG_WHY_* of pod cap, selector, unschedulable, taints
+  for (int32_t qi = 0; qi < a.nq; ++qi) {
+    const FitQuery fq = a.q[qi];
+    const int32_t tab_end = a.tab_lo + a.tab_n;
+    const int32_t end = std::min(fq.end, tab_end);
+    const int32_t vend = std::min(fq.win >= 0 ? fq.win + 1 : fq.end, tab_end);
+    int32_t out[kReasonOut] = {};
+    for (int k = 7; k < 13; ++k) out[k] = -1;
+    for (int32_t n = a.tab_lo; n < vend; ++n) {
+      const uint64_t bit = 1ull << (n & 63);
+      const size_t w = (size_t)(n >> 6);
+      if (!(a.live[w] & bit)) continue;
+      out[0]++;
+      if (n >= end || !a.cap_check) continue;  // (the node an Allocate took passed every stage)
+      const int32_t r = n - a.tab_lo, e1 = a.hoff[n + 1];
+      const bool capped = t.nt[r] - (e1 - first_undone(a.hk, a.hoff[n], e1, fq.point)) >= t.mt[r];
+      int s = -1;
+      if (capped) s = 0;
+      else if (!(a.sel_ok[(size_t)fq.cls * a.W + w] & bit)) s = 1;
+      else if (a.unsched[w] & bit) s = 2;
+      else if (!(a.taint_ok[(size_t)fq.cls * a.W + w] & bit)) s = 3;
+      if (s < 0) continue;
+      if (out[1 + kCode[s]]++ == 0) out[7 + kCode[s]] = n;
+    }
+    std::copy(out, out + kReasonOut, a.out + kReasonOut * (size_t)qi);
+  }
+}
+
+bool eval_req(const StaticTables& t, const ReqProg& r, int32_t node) {
+  switch (r.kind) {
+    case REQ_FALSE: return false;
+    case REQ_TRUE: return true;
+    case REQ_ALL:
+    case REQ_ANY:
+    case REQ_NONE: {
+      bool any = false, all = true;
+      for (int32_t w = 0; w < t.label_words; ++w) {
+        const uint64_t m = t.mask_pool[r.mask_off + w];
+        const uint64_t b = t.label_bits[(size_t)w * t.n_nodes + node] & m;
+        any |= b != 0ull;
+        all &= b == m;
+      }
+      return r.kind == REQ_ALL ? all : (r.kind == REQ_ANY ? any : !any);
+    }
+    case REQ_GT:
+    case REQ_LT: {
+      const size_t k = (size_t)r.col * t.n_nodes + node;
+      if (!t.num_ok[k]) return false;
+      return r.kind == REQ_GT ? t.num_vals[k] > r.value : t.num_vals[k] < r.value;
+    }
+    case REQ_NAME_EQ: return (int64_t)t.name_id[node] == r.value;
+    case REQ_NAME_NE: return (int64_t)t.name_id[node] != r.value;
+  }
+  return false;
+}
+
+// nodeSelector and required node affinity (vendor predicates.go:807-850)
+bool selector_ok(const StaticTables& t, const ClassProg& c, int32_t node) {
+  if (c.sel_req >= 0 && !eval_req(t, t.reqs[c.sel_req], node)) return false;
+  if (!c.has_affinity) return true;
+  for (int32_t i = 0; i < c.term_len; ++i) {
+    const TermProg tp = t.terms[c.term_off + i];
+    bool all = true;
+    for (int32_t j = 0; j < tp.req_len && all; ++j) all = eval_req(t, t.reqs[tp.req_off + j], node);
+    if (all) return true;
+  }
+  return false;
+}
+// every taint tolerated (vendor predicates.go:1489-1517)
+bool taints_ok(const StaticTables& t, const ClassProg& c, int32_t node) {
+  for (int32_t w = 0; w < t.taint_words; ++w)
+    if (t.taint_bits[(size_t)w * t.n_nodes + node] & ~t.tol_pool[c.tol_off + w]) return false;
+  return true;
+}
+
+void class_mask_run(const StaticTables& t, int32_t n_classes, int32_t W, uint64_t* class_mask) {
+  for (int32_t cls = 0; cls < n_classes; ++cls) {
+    const ClassProg c = t.classes[cls];
+    for (int32_t w = 0; w < W; ++w) {
+      uint64_t m = 0ull;
+      for (int b = 0; b < 64; ++b) {
+        const int32_t node = w * 64 + b;
+        if (node >= t.n_nodes) break;
+        const uint8_t fl = t.node_flags[node];
+        bool ok;
+        if (c.always || (fl & NF_NIL)) ok = true;  // a nil Node: the host reports it when reached
+        else if (fl & (NF_UNSCHED | NF_DEAD)) ok = false;
+        else ok = selector_ok(t, c, node) && taints_ok(t, c, node);
+        if (ok) m |= 1ull << b;
+      }
+      class_mask[(size_t)cls * W + w] = m;
+    }
+  }
+}
+
+void stage_planes_run(const StaticTables& t, int32_t n_classes, int32_t W, const StagePlanes& p) {
+  for (int32_t cls = 0; cls < n_classes; ++cls) {
+    const ClassProg c = t.classes[cls];
+    for (int32_t w = 0; w < W; ++w) {
+      uint64_t ms = 0, mt = 0, mu = 0, ml = 0;
+      for (int b = 0; b < 64; ++b) {
+        const int32_t node = w * 64 + b;
+        if (node >= t.n_nodes) break;
+        const uint8_t fl = t.node_flags[node];
+        const bool nil = (fl & NF_NIL) != 0;  // passes every stage here
+        if (nil || !(fl & NF_DEAD)) ml |= 1ull << b;
+        if (!nil && (fl & NF_UNSCHED)) mu |= 1ull << b;
+        const bool plain = c.always || nil;
+        if (plain || selector_ok(t, c, node)) ms |= 1ull << b;
+        if (plain || taints_ok(t, c, node)) mt |= 1ull << b;
+      }
+      p.sel_ok[(size_t)cls * W + w] = ms;
+      p.taint_ok[(size_t)cls * W + w] = mt;
+      if (cls == 0) {
+        p.unsched[w] = mu;
+        p.live[w] = ml;
+      }
+    }
+  }
+}
+
+// The launch with the kernel's own start / stop events around it.
+template <class F>
+hipError_t launch(hipStream_t stream, hipEvent_t start, hipEvent_t stop, F fn) {
+  if (start)
+    if (const hipError_t e = hipEventRecord(start, stream); e != hipSuccess) return e;
+  hostsim::enqueue(stream, std::move(fn));
+  if (stop) return hipEventRecord(stop, stream);
+  return hipSuccess;
+}
+
+}  // namespace
+
+// (csrc/kbg_kernels.hip firstfit_geometry: pure host code, the same rule)
+FfGeometry firstfit_geometry(int32_t G, bool full_scan) {
+  constexpr int kCUs = 256;
+  if (!full_scan) {
+    const int v = G <= 16 * kCUs ? 16 : G <= 24 * kCUs ? 24 : 32;
+    return {v, v};
+  }
+  int rows = (G + kCUs - 1) / kCUs;
+  rows = std::min(32, std::max(2, (rows + 1) & ~1));
+  return {rows <= 16 ? 16 : rows <= 24 ? 24 : 32, rows};
+}
+
+hipError_t launch_firstfit(const FirstFitArgs& a, int32_t int_mode, hipStream_t stream, hipEvent_t start,
+                           hipEvent_t stop) {
+  if (a.G <= 0) return hipSuccess;
+  const FfGeometry geo = firstfit_geometry(a.G, !a.early_exit);
+  if (a.rows <= 0 || a.rows > geo.variant) return hipErrorInvalidValue;
+  if (a.complete && a.w_hi - a.w_lo > kFfRoundWords) return hipErrorInvalidValue;
+  return launch(stream, start, stop, [a, int_mode] { firstfit_run(a, int_mode != 0); });
+}
+
+hipError_t launch_scan(const NodeSoA& n, const ScanGeom& g, const uint64_t* class_mask, const TaskRec* tasks,
+                       int32_t n_tasks, int32_t cap_check, int32_t int_mode, uint64_t* out, hipStream_t stream,
+                       hipEvent_t start, hipEvent_t stop) {
+  if (n_tasks <= 0 || g.n_chunks <= 0) return hipSuccess;
+  return launch(stream, start, stop, [n, g, class_mask, tasks, n_tasks, cap_check, int_mode, out] {
+    scan_run(n, g, class_mask, tasks, n_tasks, cap_check != 0, int_mode != 0, out);
+  });
+}
+
+hipError_t launch_select(const uint64_t* bits, int32_t w_lo, int32_t w_hi, int32_t Wl, int32_t n_rows,
+                         const uint32_t* cap_off, uint32_t* out_cand, uint32_t* out_count, hipStream_t stream,
+                         hipEvent_t start, hipEvent_t stop) {
+  if (n_rows <= 0) return hipSuccess;
+  return launch(stream, start, stop, [=] { select_run(bits, w_lo, w_hi, Wl, n_rows, cap_off, out_cand, out_count); });
+}
+
+hipError_t launch_apply(const NodeSoA& n, const NodeDelta* deltas, int32_t n_deltas, hipStream_t stream) {
+  if (n_deltas <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [n, deltas, n_deltas] {
+    for (int32_t i = 0; i < n_deltas; ++i) {
+      const NodeDelta& d = deltas[i];
+      n.idle_cpu[d.node] = d.idle[0];
+      n.idle_mem[d.node] = d.idle[1];
+      n.idle_gpu[d.node] = d.idle[2];
+      n.rel_cpu[d.node] = d.rel[0];
+      n.rel_mem[d.node] = d.rel[1];
+      n.rel_gpu[d.node] = d.rel[2];
+      n.ntasks[d.node] = d.ntasks;
+      n.maxtasks[d.node] = d.maxtasks;
+    }
+  });
+}
+
+hipError_t launch_copy16(void* dst, const void* src, size_t n16, hipStream_t stream) {
+  if (n16 == 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [dst, src, n16] { memcpy(dst, src, n16 * 16); });
+}
+
+hipError_t launch_mask_apply(uint64_t* class_mask, const MaskDelta* deltas, int32_t n_deltas, hipStream_t stream) {
+  if (n_deltas <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [class_mask, deltas, n_deltas] {
+    for (int32_t i = 0; i < n_deltas; ++i) class_mask[deltas[i].index] = deltas[i].value;
+  });
+}
+
+hipError_t launch_fitdelta(const FitArgs& a, hipStream_t stream) {
+  if (a.nq <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [a] { fitdelta_run(a); });
+}
+
+hipError_t launch_reasons(const ReasonArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.nq <= 0) return hipSuccess;
+  return launch(stream, start, stop, [a] { reasons_run(a); });
+}
+
+hipError_t launch_build_class_mask(const StaticTables& t, int32_t n_classes, int32_t W, uint64_t* class_mask,
+                                   hipStream_t stream) {
+  if (n_classes <= 0 || W <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [t, n_classes, W, class_mask] { class_mask_run(t, n_classes, W, class_mask); });
+}
+
+hipError_t launch_build_stage_planes(const StaticTables& t, int32_t n_classes, int32_t W, const StagePlanes& p,
+                                     hipStream_t stream) {
+  if (n_classes <= 0 || W <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [t, n_classes, W, p] { stage_planes_run(t, n_classes, W, p); });
+}
+
+// ---- not restated: preempt / reclaim fail with this error
+hipError_t launch_victim_scan(const VictimScan&, const VictimTables&, uint32_t*, uint32_t*, hipStream_t, hipEvent_t,
+                              hipEvent_t) {
+  return hipErrorNotSupported;
+}
+hipError_t launch_victim_big(const VictimScan&, const VictimTables&, const int32_t*, int32_t, uint32_t*, uint32_t*,
+                             uint8_t*, hipStream_t) {
+  return hipErrorNotSupported;
+}
+hipError_t launch_victim_prep(const NodeSoA&, const VictimTables&, const NodeDelta*, int32_t, const StateDelta*, int32_t,
+                              hipStream_t) {
+  return hipErrorNotSupported;
+}
+hipError_t launch_victim_prep_inline(const NodeSoA&, const VictimTables&, const VictimPrepArgs&, hipStream_t) {
+  return hipErrorNotSupported;
+}
+
+}  // namespace kbg

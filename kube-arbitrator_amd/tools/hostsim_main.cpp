@@ -1,0 +1,129 @@
+// hostsim (developer tool, never shipped): replays a kbg_snapshot_save file
+// through the session code on the simulated HIP stream, as a stand-alone
+// program — the form the sanitizer builds take (make hostsim-tsan /
+// hostsim-asan link the runtime into this executable).
+//
+//   hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions a,b,...]
+//                [--batch-tasks N] [--candidates N] [--full-scan]
+//                [--general-scan] [--repeat N]
+//
+// Each repeat opens a session, runs the actions (allocate, backfill),
+// resets the session, runs them again and closes it. OUT receives, per run of
+// the actions, the status of every call, the decision log and every node's
+// state as raw bytes, so two builds (or two schedules) are compared with cmp.
+// Exit status 0 unless the arguments or the files are unusable.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/kbgpu.h"
+
+namespace {
+
+void put(std::vector<char>& out, const void* p, size_t n) {
+  out.insert(out.end(), (const char*)p, (const char*)p + n);
+}
+void put_i32(std::vector<char>& out, int32_t v) { put(out, &v, 4); }
+
+// One run of the action list on an open session.
+void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
+                 std::vector<char>& out) {
+  std::vector<kbg_decision> dec((size_t)n_tasks + 1);
+  int32_t n = 0;
+  for (const std::string& a : actions) {
+    const kbg_status st = a == "allocate" ? kbg_allocate(s, dec.data(), (int32_t)dec.size(), &n)
+                                          : kbg_backfill(s, dec.data(), (int32_t)dec.size(), &n);
+    put_i32(out, (int32_t)st);
+    if (st != KBG_OK) {
+      fprintf(stderr, "hostsim_main: %s: status %d: %s\n", a.c_str(), (int)st, kbg_last_error());
+      return;
+    }
+  }
+  put_i32(out, n);
+  put(out, dec.data(), (size_t)n * sizeof(kbg_decision));
+  for (int32_t i = 0; i < n_nodes; ++i) {
+    kbg_node_state ns;
+    memset(&ns, 0, sizeof ns);
+    put_i32(out, (int32_t)kbg_node_state_get(s, i, &ns));
+    put(out, &ns, sizeof ns);
+  }
+}
+
+int usage() {
+  fprintf(stderr,
+          "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions allocate,backfill] [--batch-tasks N]\n"
+          "                    [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n");
+  return 2;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 3) return usage();
+  kbg_options opts;
+  memset(&opts, 0, sizeof opts);
+  std::vector<std::string> actions{"allocate"};
+  int repeat = 1;
+  for (int i = 3; i < argc; ++i) {
+    const std::string a = argv[i];
+    const bool more = i + 1 < argc;
+    if (a == "--schedule" && more) {
+      setenv("KBG_HOSTSIM_SCHEDULE", argv[++i], 1);  // read at the simulator's first call
+    } else if (a == "--actions" && more) {
+      actions.clear();
+      std::string list = argv[++i];
+      for (size_t p = 0; p <= list.size();) {
+        const size_t q = std::min(list.find(',', p), list.size());
+        const std::string name = list.substr(p, q - p);
+        if (name != "allocate" && name != "backfill") {
+          fprintf(stderr, "hostsim_main: action %s (allocate and backfill run on the simulated stream)\n", name.c_str());
+          return 2;
+        }
+        actions.push_back(name);
+        p = q + 1;
+      }
+    } else if (a == "--batch-tasks" && more) {
+      opts.batch_tasks = atoi(argv[++i]);
+    } else if (a == "--candidates" && more) {
+      opts.candidates = atoi(argv[++i]);
+    } else if (a == "--full-scan") {
+      opts.full_scan = 1;
+    } else if (a == "--general-scan") {
+      setenv("KBG_FORCE_GENERAL_SCAN", "1", 1);
+    } else if (a == "--repeat" && more) {
+      repeat = atoi(argv[++i]);
+    } else {
+      return usage();
+    }
+  }
+  kbg_snapshot_blob* blob = nullptr;
+  if (kbg_snapshot_load(argv[1], &blob) != KBG_OK) {
+    fprintf(stderr, "hostsim_main: %s: %s\n", argv[1], kbg_last_error());
+    return 2;
+  }
+  const kbg_snapshot* snap = kbg_snapshot_blob_get(blob);
+  std::vector<char> out;
+  for (int r = 0; r < repeat; ++r) {
+    kbg_session* s = nullptr;
+    const kbg_status st = kbg_session_open(snap, &opts, &s);
+    put_i32(out, (int32_t)st);
+    if (st != KBG_OK) {
+      fprintf(stderr, "hostsim_main: open: status %d: %s\n", (int)st, kbg_last_error());
+      continue;
+    }
+    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out);
+    const kbg_status rs = kbg_session_reset(s);
+    put_i32(out, (int32_t)rs);
+    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out);
+    kbg_session_close(s);
+  }
+  kbg_snapshot_blob_free(blob);
+  FILE* f = fopen(argv[2], "wb");
+  if (!f || fwrite(out.data(), 1, out.size(), f) != out.size() || fclose(f) != 0) {
+    fprintf(stderr, "hostsim_main: cannot write %s\n", argv[2]);
+    return 2;
+  }
+  return 0;
+}

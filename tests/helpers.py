@@ -111,3 +111,16 @@ def build_tools():
         fcntl.flock(f, fcntl.LOCK_EX)
         subprocess.run(["make", "-s", "-C", pkg, "tools"], check=True)
         return os.path.join(pkg, "tools", "libkbg_tools.so")
+
+
+def build_hostsim():
+    """`make hostsim` (kube-arbitrator_amd/tools/libkbg_hostsim.so and
+    hostsim_main: the session code on a simulated HIP stream, CPU only) under
+    the same lock; returns the library's path."""
+    import fcntl
+    import subprocess
+    pkg = os.path.join(ROOT, "kube-arbitrator_amd")
+    with open(os.path.join(pkg, "tools", ".build.lock"), "w") as f:
+        fcntl.flock(f, fcntl.LOCK_EX)
+        subprocess.run(["make", "-s", "-C", pkg, "-j", str(min(8, os.cpu_count() or 2)), "hostsim"], check=True)
+        return os.path.join(pkg, "tools", "libkbg_hostsim.so")

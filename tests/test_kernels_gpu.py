@@ -130,8 +130,7 @@ def test_fitdelta(probe, name):
     assert (out[4 * nq:] == ref[4 * nq:]).all(), "guard overwritten"
 
 
-@pytest.fixture(scope="module")
-def applied(probe):
+def run_apply_case(probe):
     """One run of the apply probe: the table after kbg_apply_kernel, the mask
     after kbg_mask_apply_kernel, kbg_copy16_kernel's copy, and numpy's."""
     rng = np.random.default_rng(9001)
@@ -164,6 +163,11 @@ def applied(probe):
     check_rc(probe, rc)
     want = np.frombuffer(ef.tobytes() + ei.tobytes(), dtype=np.uint8)
     return dict(table=table, want=want, mask=got_mask, want_mask=em, copy=copy)
+
+
+@pytest.fixture(scope="module")
+def applied(probe):
+    return run_apply_case(probe)
 
 
 def test_apply(applied):

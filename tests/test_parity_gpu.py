@@ -549,7 +549,9 @@ def test_staging_reuse_under_overlap():
     delta staging must not be rewritten before the stream has copied it
     (stage_acquire / stage_release), or a lost node delta shows up as a
     backfill onto a full node. Repeated in one process, where the stream runs
-    behind the host."""
+    behind the host. The deterministic version is
+    tests/test_hostsim_parity.py (the staging-race cases under the lazy
+    schedule of the simulated stream, on the CPU)."""
     fx = load_golden("fx_staging_race.json")
     ref = run_oracle(fx)
     for it in range(120):
