@@ -1,18 +1,24 @@
-// hostsim (developer tool, never shipped): every kbg::launch_* the allocate /
-// backfill / update paths reach, as plain C++ on the simulated stream of
-// hostsim_hip.cpp. Each is the contract of csrc/kbg_device.hpp restated per
-// node and per row — nothing of the kernels' waves, LDS or rounds — and
-// writes exactly the bytes the kernel writes. A launcher copies its argument
-// struct when it is called, as a kernel launch does; memory the arguments
-// point to is read when the operation runs. tests/test_hostsim_kernels.py
-// holds them to the reference the GPU kernels are held to.
+// hostsim (developer tool, never shipped): every kbg::launch_* of
+// csrc/kbg_device.hpp — the allocate / backfill / update paths and the
+// preempt / reclaim victim scan with its prep — as plain C++ on the simulated
+// stream of hostsim_hip.cpp. Each is the contract of csrc/kbg_device.hpp
+// restated per node and per row — nothing of the kernels' waves, chunks, LDS
+// or rounds — and writes exactly the bytes the kernel writes. A launcher
+// copies its argument struct when it is called, as a kernel launch does;
+// memory the arguments point to is read when the operation runs.
+// tests/test_hostsim_kernels.py holds them to the references the GPU kernels
+// are held to (tests/kernel_ref.py, tests/victim_ref.py).
 //
-// The four victim launchers are not restated: they answer
-// hipErrorNotSupported, so preempt / reclaim sessions fail cleanly.
+// The victim launchers count their launches (kbg_hostsim_launch_counts, an
+// export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
+// from them that its sessions reached the staged prep, its chunk loop and the
+// big-node launch.
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "../csrc/kbg_device.hpp"
@@ -318,9 +324,201 @@ void stage_planes_run(const StaticTables& t, int32_t n_classes, int32_t W, const
   }
 }
 
+// ---- preempt / reclaim victim scan (preempt.go:182-240, reclaim.go:106-135)
+inline bool le3(const double* r, const double* a) {  // Resource.LessEqual
+  return le(r[0], a[0], kMinMilliCPU) && le(r[1], a[1], kMinMemory) && le(r[2], a[2], kMinMilliGPU);
+}
+// Resource.Less
+inline bool less3(const double* a, const double* b) { return a[0] < b[0] && a[1] < b[1] && a[2] < b[2]; }
+// Resource.Sub (resource_info.go:100-110): false where the reference panics
+inline bool sub3(double* a, const double* r) {
+  const bool ok = le3(r, a);
+  for (int d = 0; d < 3; ++d) a[d] -= r[d];
+  return ok;
+}
+// drf.go:156-166 with helpers.Share
+inline double share3(const double* a, const double* tot) {
+  double res = 0;
+  for (int d = 0; d < 3; ++d) {
+    const double s = tot[d] == 0 ? (a[d] == 0 ? 0.0 : 1.0) : a[d] / tot[d];
+    if (s > res) res = s;
+  }
+  return res;
+}
+
+struct Alloc3 {
+  double v[3];
+};
+// A victim fn's running allocation of job / queue `id`, starting from the table's row.
+inline double* running(std::map<int32_t, Alloc3>& m, int32_t id, const double* table) {
+  auto it = m.find(id);
+  if (it == m.end()) {
+    const double* row = table + 3 * (size_t)id;
+    it = m.emplace(id, Alloc3{{row[0], row[1], row[2]}}).first;
+  }
+  return it->second.v;
+}
+
+enum Verdict : int { kMoveOn = 0, kStop = 1, kPanic = 2 };
+
+// What the reference does when the preemptor reaches the node of table row
+// `row`: PredicateFn (static class bit, the nil-node panic, the pod cap), the
+// action's preemptee filter over the node's Running candidates in
+// NodeInfo.Tasks order, the victim fns of the first tier that yields a victim
+// (gang.go:104-124, drf.go:80-105, proportion.go:161-186, intersected:
+// session_plugins.go:59-140) and validateVictims (preempt.go:242-253).
+Verdict victim_verdict(const VictimScan& p, const VictimTables& t, int32_t row) {
+  const int32_t n = p.node_lo + row;
+  if (!((t.class_mask[(size_t)p.cls * p.W + (n >> 6)] >> (n & 63)) & 1ull)) return kMoveOn;
+  if (t.panic_node[n]) return kPanic;                                       // predicates.go:122-123
+  if (p.cap_check && t.ntasks[row] >= t.maxtasks[row]) return kMoveOn;      // :125-127
+  const int32_t* jq = reinterpret_cast<const int32_t*>(t.c_jq);
+  std::vector<size_t> pre;  // candidate positions
+  for (size_t pos = (size_t)t.nt_off[n]; pos < (size_t)t.nt_off[n + 1]; ++pos) {
+    if (!t.c_run[pos]) continue;
+    const int32_t job = jq[2 * pos], queue = jq[2 * pos + 1];
+    bool f;
+    if (p.mode == VM_PREEMPT_JOBS) f = queue == p.queue && job != p.job;  // preempt.go:100-112
+    else if (p.mode == VM_PREEMPT_TASKS) f = job == p.job;                // :146-154
+    else f = queue != p.queue;                                            // reclaim.go:113-126
+    if (f) pre.push_back(pos);
+  }
+  if (pre.empty()) return kMoveOn;
+  std::vector<size_t> victims;
+  for (int32_t ti = 0; ti < p.n_tiers && victims.empty(); ++ti) {
+    const int32_t fns = p.tier_fns[ti];
+    std::vector<char> keep(pre.size(), 1);
+    if (fns & VP_GANG)
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t job = jq[2 * pre[i]];
+        if (!(t.j_min[job] <= t.j_ready[job] - 1)) keep[i] = 0;
+      }
+    if (fns & VP_DRF) {  // every preemptee subtracts from its job, in order, whatever the other fns keep
+      std::map<int32_t, Alloc3> alloc;
+      for (size_t i = 0; i < pre.size(); ++i) {
+        double* a = running(alloc, jq[2 * pre[i]], t.j_alloc);
+        if (!sub3(a, t.c_req + 3 * pre[i])) return kPanic;
+        const double rs = share3(a, t.drf_total);
+        if (!(p.ls < rs || std::fabs(p.ls - rs) <= 0.000001)) keep[i] = 0;
+      }
+    }
+    if (fns & VP_PROP) {
+      std::map<int32_t, Alloc3> alloc;
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t queue = jq[2 * pre[i] + 1];
+        const double* r = t.c_req + 3 * pre[i];
+        double* a = running(alloc, queue, t.q_alloc);
+        if (less3(a, r)) {  // skipped: the allocation stays
+          keep[i] = 0;
+          continue;
+        }
+        if (!sub3(a, r)) return kPanic;
+        if (!le3(t.q_deserved + 3 * (size_t)queue, a)) keep[i] = 0;
+      }
+    }
+    for (size_t i = 0; i < pre.size(); ++i)
+      if (keep[i]) victims.push_back(pre[i]);
+  }
+  if (victims.empty()) return kMoveOn;
+  double all[3] = {0.0, 0.0, 0.0};  // validateVictims, in victims order
+  for (size_t pos : victims)
+    for (int d = 0; d < 3; ++d) all[d] += t.c_req[3 * pos + d];
+  return less3(all, p.req) ? kMoveOn : kStop;
+}
+
+inline int32_t candidates_of(const VictimScan& p, const VictimTables& t, int32_t row) {
+  return t.nt_off[p.node_lo + row + 1] - t.nt_off[p.node_lo + row];
+}
+
+// The stop and panic bits of the range's nodes, a byte (8 nodes) at a time:
+// every byte holding a node of the range is written whole, bits past the
+// range 0, and so is the bit of a node holding more than 128 candidates
+// (launch_victim_big's). No other byte is touched.
+void victim_scan_run(const VictimScan& p, const VictimTables& t, uint32_t* stop_bits, uint32_t* panic_bits) {
+  uint8_t* stop = reinterpret_cast<uint8_t*>(stop_bits) + (p.node_lo >> 3);
+  uint8_t* panic = reinterpret_cast<uint8_t*>(panic_bits) + (p.node_lo >> 3);
+  for (int32_t r0 = 0; r0 < p.node_n; r0 += 8) {
+    uint8_t s = 0, q = 0;
+    for (int32_t row = r0; row < std::min(p.node_n, r0 + 8); ++row) {
+      if (candidates_of(p, t, row) > 128) continue;
+      const Verdict v = victim_verdict(p, t, row);
+      if (v != kMoveOn) s |= (uint8_t)(1u << (row - r0));
+      if (v == kPanic) q |= (uint8_t)(1u << (row - r0));
+    }
+    stop[r0 >> 3] = s;
+    panic[r0 >> 3] = q;
+  }
+}
+
+void victim_big_run(const VictimScan& p, const VictimTables& t, const int32_t* rows, int32_t n_rows,
+                    uint32_t* stop_bits, uint32_t* panic_bits, uint8_t* row_out) {
+  for (int32_t i = 0; i < n_rows; ++i) {
+    const Verdict v = victim_verdict(p, t, rows[i]);
+    if (row_out) {
+      row_out[i] = v == kMoveOn ? 0u : v == kStop ? 1u : 3u;  // bit 0 stop, bit 1 panic
+      continue;
+    }
+    if (v == kMoveOn) continue;
+    const int32_t n = p.node_lo + rows[i];
+    stop_bits[n >> 5] |= 1u << (n & 31);
+    if (v == kPanic) panic_bits[n >> 5] |= 1u << (n & 31);
+  }
+}
+
+void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
+  n.idle_cpu[d.node] = d.idle[0];
+  n.idle_mem[d.node] = d.idle[1];
+  n.idle_gpu[d.node] = d.idle[2];
+  n.rel_cpu[d.node] = d.rel[0];
+  n.rel_mem[d.node] = d.rel[1];
+  n.rel_gpu[d.node] = d.rel[2];
+  n.ntasks[d.node] = d.ntasks;
+  n.maxtasks[d.node] = d.maxtasks;
+}
+
+void victim_prep_run(const NodeSoA& n, const VictimTables& t, const NodeDelta* nd, int32_t nn, const StateDelta* sd,
+                     int32_t ns) {
+  for (int32_t i = 0; i < nn; ++i) node_delta_run(n, nd[i]);
+  for (int32_t i = 0; i < ns; ++i) {
+    const StateDelta& x = sd[i];
+    switch (x.kind) {
+      case 0: t.c_run[x.index] = (uint8_t)(x.v[0] != 0.0); break;
+      case 1: t.j_ready[x.index] = (int32_t)x.v[0]; break;
+      case 2: std::copy(x.v, x.v + 3, t.j_alloc + 3 * (size_t)x.index); break;
+      case 3: std::copy(x.v, x.v + 3, t.q_alloc + 3 * (size_t)x.index); break;
+    }
+  }
+}
+
+// Launch counters of the victim launchers (kbg_hostsim_launch_counts).
+enum Count : int {
+  kCountScan,
+  kCountBig,
+  kCountBigRowOut,
+  kCountPrep,
+  kCountPrepNextChunk,
+  kCountPrepInline,
+  kCountPrepInlineNodes,
+  kCountPrepInlineState,
+  kCounts
+};
+constexpr const char* kCountNames =
+    "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
+    "victim_prep_inline_nodes,victim_prep_inline_state";
+std::atomic<int64_t> g_count[kCounts];
+// Every launch of this file in order, and the staged prep's last one: a
+// staged prep that directly follows a staged prep and carries node rows, or
+// follows one that filled its state staging, is the next chunk of the same
+// victim_push (the first launch of any other push carries the touched rows of
+// a scan that ran in between, or none).
+std::atomic<uint64_t> g_seq{0};
+std::atomic<uint64_t> g_prep_seq{0};
+std::atomic<int32_t> g_prep_ns{0};
+
 // The launch with the kernel's own start / stop events around it.
 template <class F>
 hipError_t launch(hipStream_t stream, hipEvent_t start, hipEvent_t stop, F fn) {
+  g_seq++;
   if (start)
     if (const hipError_t e = hipEventRecord(start, stream); e != hipSuccess) return e;
   hostsim::enqueue(stream, std::move(fn));
@@ -418,21 +616,59 @@ hipError_t launch_build_stage_planes(const StaticTables& t, int32_t n_classes, i
   return launch(stream, nullptr, nullptr, [t, n_classes, W, p] { stage_planes_run(t, n_classes, W, p); });
 }
 
-// ---- not restated: preempt / reclaim fail with this error
-hipError_t launch_victim_scan(const VictimScan&, const VictimTables&, uint32_t*, uint32_t*, hipStream_t, hipEvent_t,
-                              hipEvent_t) {
-  return hipErrorNotSupported;
+hipError_t launch_victim_scan(const VictimScan& p, const VictimTables& t, uint32_t* stop_bits, uint32_t* panic_bits,
+                              hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (p.node_n <= 0) return hipSuccess;
+  g_count[kCountScan]++;
+  return launch(stream, start, stop, [p, t, stop_bits, panic_bits] { victim_scan_run(p, t, stop_bits, panic_bits); });
 }
-hipError_t launch_victim_big(const VictimScan&, const VictimTables&, const int32_t*, int32_t, uint32_t*, uint32_t*,
-                             uint8_t*, hipStream_t) {
-  return hipErrorNotSupported;
+
+hipError_t launch_victim_big(const VictimScan& p, const VictimTables& t, const int32_t* rows, int32_t n_rows,
+                             uint32_t* stop_bits, uint32_t* panic_bits, uint8_t* row_out, hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  g_count[row_out ? kCountBigRowOut : kCountBig]++;
+  return launch(stream, nullptr, nullptr, [p, t, rows, n_rows, stop_bits, panic_bits, row_out] {
+    victim_big_run(p, t, rows, n_rows, stop_bits, panic_bits, row_out);
+  });
 }
-hipError_t launch_victim_prep(const NodeSoA&, const VictimTables&, const NodeDelta*, int32_t, const StateDelta*, int32_t,
-                              hipStream_t) {
-  return hipErrorNotSupported;
+
+hipError_t launch_victim_prep(const NodeSoA& n, const VictimTables& t, const NodeDelta* nd, int32_t n_nodes,
+                              const StateDelta* sd, int32_t n_state, hipStream_t stream) {
+  if (n_nodes + n_state <= 0) return hipSuccess;
+  g_count[kCountPrep]++;
+  if (g_prep_seq.load() == g_seq.load() && g_seq.load() != 0 && (n_nodes > 0 || g_prep_ns.load() == kMaskDeltaCap))
+    g_count[kCountPrepNextChunk]++;
+  g_prep_ns = n_state;
+  const hipError_t e = launch(stream, nullptr, nullptr,
+                              [n, t, nd, n_nodes, sd, n_state] { victim_prep_run(n, t, nd, n_nodes, sd, n_state); });
+  g_prep_seq = g_seq.load();
+  return e;
 }
-hipError_t launch_victim_prep_inline(const NodeSoA&, const VictimTables&, const VictimPrepArgs&, hipStream_t) {
-  return hipErrorNotSupported;
+
+hipError_t launch_victim_prep_inline(const NodeSoA& n, const VictimTables& t, const VictimPrepArgs& a,
+                                     hipStream_t stream) {
+  if (a.nn + a.ns <= 0) return hipSuccess;
+  g_count[kCountPrepInline]++;
+  if (a.nn > 0) g_count[kCountPrepInlineNodes]++;
+  if (a.ns > 0) g_count[kCountPrepInlineState]++;
+  // the deltas travel in the arguments: copied now (an uninitialised tail is not read)
+  std::vector<NodeDelta> nd(a.nd, a.nd + a.nn);
+  std::vector<StateDelta> sd(a.sd, a.sd + a.ns);
+  return launch(stream, nullptr, nullptr, [n, t, nd = std::move(nd), sd = std::move(sd)] {
+    victim_prep_run(n, t, nd.data(), (int32_t)nd.size(), sd.data(), (int32_t)sd.size());
+  });
 }
 
 }  // namespace kbg
+
+// The launch counters since the last reset, in the order of
+// kbg_hostsim_launch_count_names (comma separated). Exported by
+// libkbg_hostsim.so only (tools/hostsim.map); not part of include/kbgpu.h.
+extern "C" const char* kbg_hostsim_launch_count_names() { return kbg::kCountNames; }
+extern "C" int32_t kbg_hostsim_launch_counts(int64_t* out, int32_t cap) {
+  for (int i = 0; i < kbg::kCounts && i < cap; ++i) out[i] = kbg::g_count[i].load();
+  return kbg::kCounts;
+}
+extern "C" void kbg_hostsim_launch_counts_reset() {
+  for (auto& c : kbg::g_count) c = 0;
+}

@@ -7,10 +7,12 @@
 //                [--batch-tasks N] [--candidates N] [--full-scan]
 //                [--general-scan] [--repeat N]
 //
-// Each repeat opens a session, runs the actions (allocate, backfill),
-// resets the session, runs them again and closes it. OUT receives, per run of
-// the actions, the status of every call, the decision log and every node's
-// state as raw bytes, so two builds (or two schedules) are compared with cmp.
+// Each repeat opens a session, runs the actions (reclaim, allocate, backfill,
+// preempt, in the order given), resets the session, runs them again and
+// closes it. OUT receives, per run of the actions, the status of every call,
+// the decision log (Allocate and Pipeline decisions) with the action behind
+// each decision, the eviction log and every node's state as raw bytes, so two
+// builds (or two schedules) are compared with cmp.
 // Exit status 0 unless the arguments or the files are unusable.
 #include <cstdio>
 #include <cstdlib>
@@ -27,22 +29,45 @@ void put(std::vector<char>& out, const void* p, size_t n) {
 }
 void put_i32(std::vector<char>& out, int32_t v) { put(out, &v, 4); }
 
-// One run of the action list on an open session.
+kbg_status run_action(kbg_session* s, const std::string& a, kbg_decision* out, int32_t cap, int32_t* n) {
+  if (a == "allocate") return kbg_allocate(s, out, cap, n);
+  if (a == "backfill") return kbg_backfill(s, out, cap, n);
+  if (a == "reclaim") return kbg_reclaim(s, out, cap, n);
+  return kbg_preempt(s, out, cap, n);
+}
+
+// One run of the action list on an open session, through the C ABI calls the
+// Python wrapper makes (kbgpu/actions.py): an action the reference would
+// panic in (KBG_E_REF_PANIC) ends the list, and what the cycle logged up to
+// there is still written.
 void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
                  std::vector<char>& out) {
   std::vector<kbg_decision> dec((size_t)n_tasks + 1);
   int32_t n = 0;
   for (const std::string& a : actions) {
-    const kbg_status st = a == "allocate" ? kbg_allocate(s, dec.data(), (int32_t)dec.size(), &n)
-                                          : kbg_backfill(s, dec.data(), (int32_t)dec.size(), &n);
+    const kbg_status st = run_action(s, a, dec.data(), (int32_t)dec.size(), &n);
     put_i32(out, (int32_t)st);
+    if (st == KBG_E_REF_PANIC) break;
     if (st != KBG_OK) {
       fprintf(stderr, "hostsim_main: %s: status %d: %s\n", a.c_str(), (int)st, kbg_last_error());
       return;
     }
   }
+  // the decision log (Allocate and Pipeline decisions of every action) and the action behind each
   put_i32(out, n);
   put(out, dec.data(), (size_t)n * sizeof(kbg_decision));
+  std::vector<int32_t> acts((size_t)n + 1);
+  int32_t na = 0;
+  put_i32(out, (int32_t)kbg_decision_actions_get(s, acts.data(), (int32_t)acts.size(), &na));
+  put_i32(out, na);
+  put(out, acts.data(), (size_t)na * sizeof(int32_t));
+  // the committed evictions of reclaim / preempt, in commit order
+  int32_t ne = 0;
+  put_i32(out, (int32_t)kbg_evictions_get(s, nullptr, 0, &ne));
+  std::vector<kbg_eviction> ev((size_t)ne + 1);
+  put_i32(out, (int32_t)kbg_evictions_get(s, ev.data(), ne, &ne));
+  put_i32(out, ne);
+  put(out, ev.data(), (size_t)ne * sizeof(kbg_eviction));
   for (int32_t i = 0; i < n_nodes; ++i) {
     kbg_node_state ns;
     memset(&ns, 0, sizeof ns);
@@ -53,8 +78,9 @@ void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_
 
 int usage() {
   fprintf(stderr,
-          "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions allocate,backfill] [--batch-tasks N]\n"
-          "                    [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n");
+          "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions reclaim,allocate,backfill,preempt]\n"
+          "                    [--batch-tasks N] [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n"
+          "  --actions: any of reclaim, allocate, backfill, preempt, run in the order given (default allocate)\n");
   return 2;
 }
 
@@ -77,8 +103,8 @@ int main(int argc, char** argv) {
       for (size_t p = 0; p <= list.size();) {
         const size_t q = std::min(list.find(',', p), list.size());
         const std::string name = list.substr(p, q - p);
-        if (name != "allocate" && name != "backfill") {
-          fprintf(stderr, "hostsim_main: action %s (allocate and backfill run on the simulated stream)\n", name.c_str());
+        if (name != "allocate" && name != "backfill" && name != "reclaim" && name != "preempt") {
+          fprintf(stderr, "hostsim_main: unknown action %s (reclaim, allocate, backfill, preempt)\n", name.c_str());
           return 2;
         }
         actions.push_back(name);

@@ -8,16 +8,20 @@ in KBG_HOSTSIM_SCHEDULE (the simulator reads it once per process).
     python tests/hostsim_worker.py parity CASES.json OUT.json
     python tests/hostsim_worker.py snapshots CASES.json DIR
 
-kernels: every seeded case of tests/kernel_cases.py through the probes
-(tools/kernel_probe.cpp compiled against the simulator), compared here with
-tests/kernel_ref.py's comparators; OUT.json maps a case id to its list of
-differences. parity: every case of CASES.json (test_hostsim_parity.py's
-specs) through the product path (kbgpu.fixture.run_fixture with KBG_LIB_PATH
-pointing at the library); OUT.json maps a case id to the outputs in the
-oracle's schema, which the parent compares with the oracle's. snapshots: the
-kbg_snapshot of every case saved as DIR/<id>.kbgs (kbg_snapshot_save) with
-DIR/manifest.json naming each one's actions, for tools/hostsim_main
-(tests/test_hostsim_sanitizers.py).
+kernels: every seeded case of tests/kernel_cases.py and tests/victim_ref.py
+(both output modes, and the launches the victim probe must refuse) through
+the probes (tools/kernel_probe.cpp compiled against the simulator), compared
+here with tests/kernel_ref.py's and tests/victim_ref.py's comparators;
+OUT.json maps a case id to its list of differences. parity: every case of
+CASES.json (test_hostsim_parity.py's specs, reclaim / preempt sessions
+included) through the product path (kbgpu.fixture.run_fixture with
+KBG_LIB_PATH pointing at the library); OUT.json maps a case id to the outputs
+in the oracle's schema, which the parent compares with the oracle's, the
+session's victim counters of kbg_stats and the launches hostsim counted per
+victim launcher during the case. snapshots: the kbg_snapshot of every case
+saved as DIR/<id>.kbgs (kbg_snapshot_save) with DIR/manifest.json naming each
+one's actions (any of reclaim, allocate, backfill, preempt), for
+tools/hostsim_main (tests/test_hostsim_sanitizers.py).
 """
 import ctypes
 import json
@@ -114,12 +118,25 @@ def kernels(out_path):
             test(L, *args)
         except AssertionError as e:
             return [str(e) or "assertion failed"]
+        except Exception as e:  # (check_rc ends a pytest run on a probe's HIP error: here it is the case's failure)
+            return [f"{type(e).__name__}: {e}"]
         return []
 
     for n in rr.NODE_COUNTS:
         res[f"stage_mask/n{n}"] = failures(trk.test_stage_mask, n)
     for name in sorted(rr.REASON_CASES):
         res["reasons/" + name] = failures(trk.test_reasons, name)
+
+    # the victim launchers (prep, scan, big-node launch) in both output modes, and the launches the
+    # probe must refuse: the bodies of tests/test_victim_kernels_gpu.py on this library
+    import test_victim_kernels_gpu as tvk
+    import victim_ref as vr
+    for name in vr.NAMES:
+        for out_mode, mode in enumerate(("mapped", "device")):
+            res[f"victim/{name}-{mode}"] = failures(tvk.test_victim_scan, name, out_mode)
+    for i, (over, mutate, null, what) in enumerate(tvk.ILLEGAL):
+        res[f"victim_reject/{i:02d}-{what.replace(' ', '_')}"] = \
+            failures(tvk.test_victim_probe_rejects_illegal_launches, over, mutate, null, what)
 
     a = run_apply_case(L)  # the case of test_kernels_gpu.py's `applied` fixture
     n = len(a["want"])
@@ -132,6 +149,43 @@ def kernels(out_path):
 
 
 # ------------------------------------------------------------------- parity
+def staged_rows_fixture(nodes=24, same=20, other=4):
+    """A hand-built reclaim session whose staged prep matters to the next scan.
+    Every node (4 CPUs, 3 pods at most) runs two 2000m tasks of queue q1. Queue
+    q2 holds `same` Pending one-task jobs of one shape (2000m): the first is
+    scanned, the others are answered from the kept stop maps (gang decides, so
+    the maps survive), each evicting one task of the next node and pipelining
+    onto it — which brings that node to its pod cap. Then `other` jobs of
+    another shape (1000m) force a new scan: victim_push now holds `same`
+    touched rows, more than the inline arguments take, and with a small
+    batch_tasks it stages them in several chunks. A chunk whose staging is
+    rewritten before its launch read it leaves earlier rows below their cap
+    on the device, the scan stops at node 0 again, and the eviction log
+    differs from the oracle's."""
+    nds = [{"name": f"n{i:02d}", "allocatable": {"cpu": "4", "memory": "16Gi", "pods": "3"}, "labels": {}}
+           for i in range(nodes)]
+    pods, pgs = [], []
+
+    def job(name, queue, ts, n_tasks, cpu, placed):
+        pgs.append({"namespace": "ns", "name": name, "minMember": 1, "queue": queue,
+                    "creationTimestamp": ts * 1_000_000_000})
+        for t in range(n_tasks):
+            node = placed[t] if placed else ""
+            pods.append({"uid": f"{name}-{t:02d}", "namespace": "ns", "name": f"{name}-{t:02d}",
+                         "phase": "Running" if placed else "Pending", "nodeName": node,
+                         "annotations": {"scheduling.k8s.io/group-name": name},
+                         "containers": [{"requests": {"cpu": f"{cpu}m", "memory": "1Gi"}}]})
+
+    for j in range(0, nodes, 4):  # a running job holds both slots of four nodes
+        job(f"run{j:02d}", "q1", 0, 8, 2000, [nds[j + k // 2]["name"] for k in range(8)])
+    for j in range(same):
+        job(f"same{j:02d}", "q2", 100 + j, 1, 2000, None)
+    for j in range(other):
+        job(f"other{j:02d}", "q2", 500 + j, 1, 1000, None)
+    return {"name": "staged-rows", "tiers": None, "nodes": nds, "pods": pods, "podGroups": pgs,
+            "queues": [{"name": "q1", "weight": 1}, {"name": "q2", "weight": 1}], "actions": ["reclaim"]}
+
+
 def make_fixture(c):
     """The fixture of a case spec (test_hostsim_parity.py CASES); the parent
     builds the same one for the oracle."""
@@ -148,6 +202,14 @@ def make_fixture(c):
         fx = synth.affinity_fixture(a)
     elif g == "dupkey":
         fx = synth.dupkey_fixture(a)
+    elif g == "contended":
+        fx = synth.contended_fixture(a, **kw)
+    elif g == "contended_dupkey":
+        fx = synth.contended_dupkey_fixture(a, **kw)
+    elif g == "contended_config":
+        fx = synth.contended_config(**kw)
+    elif g == "staged_rows":
+        fx = staged_rows_fixture(**kw)
     elif g == "saturated":
         fx = synth.saturated_config(**kw)
     elif g == "deep":
@@ -161,16 +223,22 @@ def make_fixture(c):
         fx["options"] = {"heapDownRule": "go1.13"}
     if "actions" in c:
         fx["actions"] = c["actions"]
-    if c.get("only_allocate_backfill"):  # the victim launchers are not simulated
+    if c.get("only_allocate_backfill"):  # (the cases from before the victim launchers were simulated)
         fx["actions"] = [a for a in (fx.get("actions") or ["allocate"]) if a in ("allocate", "backfill")] or ["allocate"]
     return fx
 
 
-def run_chain(c):
+def victim_stats(ssn):
+    st = ssn.stats()
+    return {k: int(getattr(st, k)) for k in ("victim_scans", "victim_tries", "victim_host_evals")}
+
+
+def run_chain(c, stats):
     """A resident session over churn rounds (helpers.churn_chain): each
     snapshot opened fresh, and the session opened at S_0 and updated round by
     round (kbg_session_update) must make the fresh open's cycle. Returns the
-    fresh outputs per round."""
+    fresh outputs per round; `stats` receives the resident session's
+    victim_stats after each round, summed."""
     from helpers import churn_chain
     from kbgpu import _abi
     from kbgpu.fixture import run_fixture
@@ -194,6 +262,8 @@ def run_chain(c):
             except _abi.KbgError as e:
                 assert e.status == "ref_panic", e
                 got = {"status": "ref_panic"}
+        for k, v in victim_stats(state["ssn"]).items():
+            stats[k] = stats.get(k, 0) + v
         _same_cycle(got, fresh)
         return fresh
 
@@ -237,6 +307,11 @@ def parity(cases_path, out_path):
     from kbgpu.fixture import run_fixture
     with open(cases_path) as f:
         cases = json.load(f)
+    # hostsim's launch counters of the victim launchers (tools/hostsim_kernels.cpp), per case
+    H = ctypes.CDLL(LIB)
+    H.kbg_hostsim_launch_count_names.restype = ctypes.c_char_p
+    names = H.kbg_hostsim_launch_count_names().decode().split(",")
+    counts = (ctypes.c_int64 * len(names))()
     res = {}
     for c in cases:
         t0 = time.time()
@@ -244,9 +319,11 @@ def parity(cases_path, out_path):
             os.environ["KBG_FORCE_GENERAL_SCAN"] = "1"
         else:
             os.environ.pop("KBG_FORCE_GENERAL_SCAN", None)
+        H.kbg_hostsim_launch_counts_reset()
         try:
             if c["gen"] == "chain":
-                rec = {"chain": run_chain(dict(c, gen=c["base"]))}
+                stats = {}
+                rec = {"chain": run_chain(dict(c, gen=c["base"]), stats), "stats": stats}
             elif c["gen"] == "reasons":
                 run_reasons(c)
                 rec = {}
@@ -255,10 +332,13 @@ def parity(cases_path, out_path):
                 rec = {"out": got}
                 if ssn:
                     rec["int_scan"] = ssn.stats().int_scan
+                    rec["stats"] = victim_stats(ssn)
                     ssn.close()
         except Exception as e:  # the case fails in the parent; the other cases still run
             # (a wrong decision can also end the host replay: kbgpu.api.RefPanic on a full node)
             rec = {"error": f"{type(e).__name__}: {e}"}
+        assert H.kbg_hostsim_launch_counts(counts, len(names)) == len(names)
+        rec["launches"] = {k: int(v) for k, v in zip(names, counts) if v}
         rec["s"] = round(time.time() - t0, 3)
         res[c["id"]] = rec
     with open(out_path, "w") as f:

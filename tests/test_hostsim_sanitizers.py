@@ -3,10 +3,13 @@ hostsim's simulated HIP stream: tools/hostsim_main (a stand-alone program; the
 sanitizer runtime is linked into it — nothing is preloaded and no sanitizer
 build is loaded into Python) replays saved snapshots of sessions whose
 allocate is contended — the Predictor thread runs beside the committer, lists
-are cut, staging is reused — under both schedules and three batch sizes. Each
-sanitizer build must end with status 0, print no report, and write the bytes
-the plain build writes (decision log and node state of the cycle and of its
-repeat after kbg_session_reset).
+are cut, staging is reused — and of contended sessions under their own reclaim
+/ preempt action lists (kbg_victims.ipp: the inline and the staged prep, the
+kept stop maps, host_stop on huge nodes, discarded statements, class masks
+following pod affinity and host ports), under both schedules and three batch
+sizes. Each sanitizer build must end with status 0, print no report, and write
+the bytes the plain build writes (decision log with its actions, eviction log
+and node state of the cycle and of its repeat after kbg_session_reset).
 
 CPU only and opt-in: skipped unless KBG_HOSTSIM_SANITIZE=1 (the sanitizer
 builds of the host sources take a few minutes to compile). Never marked gpu."""
@@ -33,6 +36,13 @@ SNAPSHOTS = [
     dict(id="affinity27", gen="affinity", arg=27, **FUZZ),
     dict(id="staging-race", gen="golden", arg="fx_staging_race.json", **FUZZ),
     dict(id="deep8193", gen="deep", arg=8193),
+    # reclaim / preempt with the fixtures' own action lists (tests/test_hostsim_parity.py's victim cases)
+    dict(id="contended115", gen="contended", arg=115),
+    dict(id="contended-large56", gen="contended", arg=5056, kw=dict(nodes=40, jobs=30, tasks=10, queues=3)),
+    dict(id="victim-affinity100", gen="contended", arg=7100, kw=dict(nodes=12, jobs=14, tasks=8, aff=0.5)),
+    dict(id="victim-ports62", gen="contended", arg=8062, kw=dict(nodes=12, jobs=14, tasks=8, ports=0.4)),
+    dict(id="victim-huge5", gen="contended", arg=9505, kw=dict(big=True, huge=True, nodes=2, jobs=240, tasks=30)),
+    dict(id="staged-rows", gen="staged_rows"),  # (batch1 / batch3: the staged prep in several chunks)
 ]
 REPORT = ("ThreadSanitizer", "AddressSanitizer", "LeakSanitizer", "UndefinedBehaviorSanitizer", "runtime error:")
 

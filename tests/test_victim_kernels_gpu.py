@@ -96,7 +96,9 @@ def _dup_state(a):
     a["sd"][9]["kind"], a["sd"][9]["index"] = a["sd"][1]["kind"], a["sd"][1]["index"]
 
 
-@pytest.mark.parametrize("over,mutate,null,what", [
+# (over, mutate, null, what): launches try_task would never produce (tests/hostsim_worker.py runs the same list
+# through hostsim's probe)
+ILLEGAL = [
     (None, None, "j_min", "null"), (None, None, "row_out", "null"),
     (dict(node_lo=32), None, None, "node_lo"), (dict(node_lo=64, node_n=10), None, None, "node range"),
     (dict(n_nodes=200, W=1), None, None, "n_nodes"), (dict(node_n=0), None, None, "node range"),
@@ -112,7 +114,10 @@ def _dup_state(a):
     (dict(nn=17), None, None, "prep"), (dict(ns=49), None, None, "prep"), (dict(prep=3), None, None, "prep"),
     (dict(prep=0), None, None, "prep"), (dict(n_rows=1), None, None, "n_rows"),
     (dict(out_mode=2), None, None, "out_mode"),
-])
+]
+
+
+@pytest.mark.parametrize("over,mutate,null,what", ILLEGAL)
 def test_victim_probe_rejects_illegal_launches(probe, over, mutate, null, what):
     """Nothing try_task would never produce reaches the device: the probe
     answers -2 with a message and leaves every buffer alone."""
