@@ -661,6 +661,50 @@ typedef struct kbg_job_reasons {
  * (KBG_E_INVALID otherwise). Sessions over a communicator are
  * KBG_E_UNSUPPORTED; sessions whose shards are all local work. */
 kbg_status kbg_job_reasons_get(kbg_session* s, int32_t job, kbg_job_reasons* out);
+
+/* Why reclaim or preempt would find no victims for a job's next Pending task
+ * (additive within KBG_ABI_VERSION 13). For the job's first Pending task in
+ * TaskOrderFn order, every live node of ssn.Nodes is evaluated against the
+ * session as it is NOW (node, job and queue state after the actions run so
+ * far), exactly as the next try of that task in the given mode would, and goes
+ * under exactly one cause, the first that applies in the reference's order
+ * (preempt.go:181-202, reclaim.go:112-150, session_plugins.go:59-140):
+ *   0..5 KBG_WHY_*            PredicateFn returned an error at that stage
+ *   6 KBG_VWHY_NO_PREEMPTEES  no Running task of the node passes the mode's filter
+ *   7 KBG_VWHY_NO_VICTIMS     Preemptable / Reclaimable returned nothing in every tier
+ *   8 KBG_VWHY_NOT_ENOUGH     validateVictims: the victims' sum is Less than Resreq
+ *   9 KBG_VWHY_VICTIMS        validated victims: the action would evict and pipeline here
+ *  10 KBG_VWHY_PANIC          nil Node under the predicates plugin, or a
+ *                             Resource.Sub underflow in a victim fn of a consulted tier
+ * fn_empty[f] (gang, drf, proportion) counts the NO_VICTIMS nodes where some
+ * tier enables fn f and f alone, over the node's whole preemptee list, keeps
+ * nobody; the three are not exclusive, and a node whose fns each keep someone
+ * but share nobody is in none of them. */
+enum { KBG_VMODE_PREEMPT_JOBS = 0, KBG_VMODE_PREEMPT_TASKS = 1, KBG_VMODE_RECLAIM = 2 };
+enum {
+  KBG_VWHY_NO_PREEMPTEES = 6,
+  KBG_VWHY_NO_VICTIMS = 7,
+  KBG_VWHY_NOT_ENOUGH = 8,
+  KBG_VWHY_VICTIMS = 9,
+  KBG_VWHY_PANIC = 10,
+  KBG_VWHY_COUNT = 11
+};
+typedef struct kbg_victim_why {
+  int32_t valid;          /* 0: the job has no Pending task now; nothing below is set */
+  int32_t task;           /* the job's first Pending task in TaskOrderFn order */
+  int32_t visited;        /* live nodes == sum(count) */
+  int32_t queue_overused; /* RECLAIM only: Overused(queue) holds now (reclaim.go:88), so reclaim would not try */
+  int32_t count[11];
+  int32_t first_node[11]; /* lowest node index per cause, -1 when none */
+  int32_t fn_empty[3];    /* gang, drf, proportion */
+  int32_t reserved[3];
+} kbg_victim_why;
+/* jobs == NULL: every job, out holds n_jobs == the session's job count
+ * entries; otherwise out[i] describes jobs[i]. Legal any time after the
+ * cycle's first action (KBG_E_INVALID before it, and on a session opened
+ * without kbg_options.reasons); KBG_E_UNSUPPORTED over a communicator. The
+ * call changes nothing: every later action returns what it would have. */
+kbg_status kbg_victim_reasons(kbg_session* s, int32_t mode, const int32_t* jobs, int32_t n_jobs, kbg_victim_why* out);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

@@ -382,4 +382,48 @@ struct VictimPrepArgs {
 hipError_t launch_victim_prep_inline(const NodeSoA& n, const VictimTables& t, const VictimPrepArgs& a,
                                      hipStream_t stream);
 
+// Why a victim scan found nothing (kbg_victim_reasons). Every live node of
+// the range goes under exactly one cause for each of nq queries (a query is a
+// VictimScan; all of a launch share n_nodes, W, node_lo and node_n), the first
+// that applies:
+//   a node whose `live` bit is clear is not counted at all;
+//   panic_node                                          -> kWhyPanic;
+//   cap_check: ntasks >= maxtasks -> 0 (pod cap), sel_ok clear -> 1,
+//     unsched set -> 3, taint_ok clear -> 4 (KBG_WHY_* codes; class_mask is
+//     not read: the stage planes name the stage);
+//   no Running candidate passes the mode's filter        -> kWhyNoPreemptees;
+//   a Sub underflow in a tier the walk reaches           -> kWhyPanic;
+//   every tier's intersection empty, or n_tiers == 0     -> kWhyNoVictims;
+//   the victims' sum Less than req                       -> kWhyNotEnough;
+//   otherwise                                            -> kWhyVictims.
+// Row q of `out` (kVictimWhyOut words): count[kWhyCauses], first_node
+// [kWhyCauses] (lowest global node of the cause, -1 none), fn_empty[3]: the
+// kWhyNoVictims nodes on which fn f (gang, drf, proportion), enabled in some
+// tier, keeps nobody of the node's whole preemptee list by itself.
+// launch_victim_why sets every row to its empty value and counts the nodes of
+// up to 128 candidates; launch_victim_why_big, after it on the same stream,
+// adds the rows of 129..kMaxNodeCandidates candidates (launch_victim_big's
+// list). Nodes holding more are in neither. `out` is device memory: the
+// workgroups add to it with atomics.
+enum VictimWhy : int32_t {
+  kWhyNoPreemptees = 6,
+  kWhyNoVictims = 7,
+  kWhyNotEnough = 8,
+  kWhyVictims = 9,
+  kWhyPanic = 10,
+  kWhyCauses = 11
+};
+constexpr int kVictimWhyOut = 2 * kWhyCauses + 3;
+struct VictimWhyArgs {
+  const VictimScan* q;  // [nq] staged in device memory
+  int32_t nq;
+  int32_t n_nodes, W, node_lo, node_n;                  // as every query's
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  int32_t* out;                                         // [nq][kVictimWhyOut]
+};
+hipError_t launch_victim_why(const VictimWhyArgs& a, const VictimTables& t, hipStream_t stream,
+                             hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, const int32_t* rows, int32_t n_rows,
+                                 hipStream_t stream);
+
 }  // namespace kbg

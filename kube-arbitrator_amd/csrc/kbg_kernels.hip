@@ -1250,6 +1250,235 @@ hipError_t launch_victim_scan(const VictimScan& p, const VictimTables& t, uint32
   return hipGetLastError();
 }
 
+// ------------------------------------------------- victim reasons
+// kbg_victim_reasons: the same per-node walk as victim_candidates, kept as a
+// function of its own so that the scan kernels above stay the code they were.
+// It cannot leave at the class bit (the stage planes name the stage instead)
+// and it walks every tier, keeping each fn's own ballot apart from the
+// intersection. The result is wave-uniform: the cause in the low byte and,
+// for kWhyNoVictims, the fns whose own result is empty (VictimPlugin bits)
+// from bit 8.
+template <int NCH, bool LDS = false>
+__device__ uint32_t victim_why_candidates(const VictimScan& p, const VictimTables& t, int off, int L, int lane,
+                                          const VCand& c0, uint64_t* lds_masks = nullptr) {
+  constexpr int PM = 0, TM = 1, VM = 2;
+  const int nch = (L + 63) >> 6;  // <= NCH
+  ChunkMasks<NCH, LDS> cm;
+  cm.lds = lds_masks;
+  cm.lane = lane;
+  uint64_t any_pm = 0ull;
+#pragma unroll
+  for (int h = 0; h < NCH; ++h) {
+    const uint64_t m = h < nch ? __ballot((h == 0 ? c0 : load_cand(p, t, off, L, h * 64 + lane)).f) : 0ull;
+    cm.set(PM, h, m);
+    any_pm |= m;
+  }
+  if (!any_pm) return kWhyNoPreemptees;
+  const bool g0 = c0.job >= 0 && t.j_min[c0.job] <= t.j_ready[c0.job] - 1;
+  bool panic = false;
+  bool victims = false;
+  uint32_t empty = 0u;  // fns of a walked tier whose own result is empty
+  for (int ti = 0; ti < p.n_tiers && !victims && !panic; ++ti) {
+    const int fns = p.tier_fns[ti];
+    bool any = false;
+    uint32_t own = 0u;  // fns that keep some preemptee by themselves
+#pragma unroll
+    for (int h = 0; h < NCH; ++h) {
+      if (h >= nch) {
+        cm.set(TM, h, 0ull);
+        continue;
+      }
+      const VCand c = h == 0 ? c0 : load_cand(p, t, off, L, h * 64 + lane);
+      const uint64_t pmh = cm.get(PM, h);
+      uint64_t m = pmh;
+      if (fns & VP_GANG) {  // gang.go:104-124
+        const uint64_t g = pmh & __ballot(h == 0 ? g0 : (c.job >= 0 && t.j_min[c.job] <= t.j_ready[c.job] - 1));
+        if (g) own |= VP_GANG;
+        m &= g;
+      }
+      if (fns & (VP_DRF | VP_PROP)) {
+        const bool on = (pmh >> lane) & 1ull;
+        double xd[3], xp[3];
+        for (int d = 0; d < 3; ++d) {
+          xd[d] = on && (fns & VP_DRF) ? t.j_alloc[3 * (size_t)c.job + d] : 0.0;
+          xp[d] = on && (fns & VP_PROP) ? t.q_alloc[3 * (size_t)c.queue + d] : 0.0;
+        }
+        bool lpanic = false, vp = false;
+        for (int h2 = 0; h2 < h; ++h2)  // preemptees of earlier chunks (all before this lane's k)
+          for (uint64_t b = cm.get(PM, h2); b; b &= b - 1) {
+            const size_t p2 = (size_t)off + h2 * 64 + __builtin_ctzll(b);  // wave-uniform
+            const int2 jq2 = t.c_jq[p2];
+            const double r2[3] = {t.c_req[3 * p2], t.c_req[3 * p2 + 1], t.c_req[3 * p2 + 2]};
+            if (on) apply_preemptee(t, fns, jq2.x, jq2.y, r2, false, c.job, c.queue, xd, xp, lpanic, vp);
+          }
+        for (uint64_t b = pmh; b; b &= b - 1) {  // this chunk, in order, while k2 <= k
+          const int l2 = __builtin_ctzll(b);
+          const int32_t j2 = rl_i(c.job, l2);
+          const int32_t q2 = rl_i(c.queue, l2);
+          const double r2[3] = {rl_d(c.r[0], l2), rl_d(c.r[1], l2), rl_d(c.r[2], l2)};
+          if (on && l2 <= lane) apply_preemptee(t, fns, j2, q2, r2, l2 == lane, c.job, c.queue, xd, xp, lpanic, vp);
+        }
+        bool vd = false;
+        if ((fns & VP_DRF) && on) {
+          const double rs = share3(xd, t.drf_total);
+          vd = p.ls < rs || fabs(p.ls - rs) <= 0.000001;
+        }
+        if (fns & VP_DRF) {
+          const uint64_t d = __ballot(vd);  // (set on preemptee lanes only)
+          if (d) own |= VP_DRF;
+          m &= d;
+        }
+        if (fns & VP_PROP) {
+          const uint64_t q = __ballot(vp);
+          if (q) own |= VP_PROP;
+          m &= q;
+        }
+        if (__ballot(lpanic) != 0ull) panic = true;
+      }
+      cm.set(TM, h, m);
+      any = any || m != 0ull;
+    }
+    empty |= (uint32_t)fns & ~own;
+    if (!panic && any) {
+#pragma unroll
+      for (int h = 0; h < NCH; ++h) cm.set(VM, h, cm.get(TM, h));
+      victims = true;
+    }
+  }
+  if (panic) return kWhyPanic;
+  if (!victims) return kWhyNoVictims | (empty << 8);
+  double all[3] = {0.0, 0.0, 0.0};  // validateVictims (preempt.go:242-253), in victims order
+#pragma unroll
+  for (int h = 0; h < NCH; ++h) {
+    const uint64_t vmh = cm.get(VM, h);
+    if (!vmh) continue;
+    const VCand c = h == 0 ? c0 : load_cand(p, t, off, L, h * 64 + lane);
+    for (uint64_t b = vmh; b; b &= b - 1) {
+      const int l2 = __builtin_ctzll(b);
+      all[0] += rl_d(c.r[0], l2);
+      all[1] += rl_d(c.r[1], l2);
+      all[2] += rl_d(c.r[2], l2);
+    }
+  }
+  return res_less3(all, p.req) ? kWhyNotEnough : kWhyVictims;
+}
+
+// The cause of table row `row` for query p (wave-uniform), 0xffffffff when
+// this kernel does not count the node: not live, or its candidates belong to
+// the other kernel (NCH_MAX <= 2: more than 128; else: fewer than 129 or more
+// than kMaxNodeCandidates).
+template <int NCH_MAX>
+__device__ __forceinline__ uint32_t victim_why_node(const VictimWhyArgs& a, const VictimScan& p, const VictimTables& t,
+                                                    int row, int lane, uint64_t* lds_masks = nullptr) {
+  constexpr uint32_t kSkip = 0xffffffffu;
+  const int n = a.node_lo + row;
+  const int off = t.nt_off[n];
+  const int L = t.nt_off[n + 1] - off;
+  if (NCH_MAX <= 2 ? L > 128 : (L <= 128 || L > kMaxNodeCandidates)) return kSkip;
+  const VCand c0 = load_cand(p, t, off, L, lane);  // requested before the node's own tests resolve
+  const int w = n >> 6;
+  const uint64_t bit = 1ull << (n & 63);
+  if (!(a.live[w] & bit)) return kSkip;
+  if (t.panic_node[n]) return kWhyPanic;  // SetNode(nil) inside PredicateFn (predicates.go:122-123)
+  if (p.cap_check) {                      // the first failing stage in the reference's order (:125-183)
+    if (t.ntasks[row] >= t.maxtasks[row]) return 0u;
+    if (!(a.sel_ok[(size_t)p.cls * a.W + w] & bit)) return 1u;
+    if (a.unsched[w] & bit) return 3u;
+    if (!(a.taint_ok[(size_t)p.cls * a.W + w] & bit)) return 4u;
+  }
+  if (NCH_MAX > 2) {
+    uint32_t key;
+    [[clang::always_inline]] key = victim_why_candidates<NCH_MAX, true>(p, t, off, L, lane, c0, lds_masks);
+    return key;
+  }
+  if (L <= 64) return victim_why_candidates<1>(p, t, off, L, lane, c0);
+  return victim_why_candidates<2>(p, t, off, L, lane, c0);
+}
+
+__global__ __launch_bounds__(256) void kbg_victim_why_init_kernel(int32_t* __restrict__ out, int32_t nq) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nq * kVictimWhyOut) return;
+  const int k = i % kVictimWhyOut;
+  out[i] = k >= kWhyCauses && k < 2 * kWhyCauses ? -1 : 0;
+}
+
+// Grid (node blocks, queries); a workgroup is kVictimBlockWaves waves, one
+// node each, as in kbg_victim_kernel. The query is read from the staged array
+// at a wave-uniform address. The workgroup's counts, minima and fn counts
+// gather in LDS; after the barrier each non-zero slot goes to the query's row
+// with one atomic. The minima are unsigned, so the empty value -1 is the
+// largest.
+__global__ __launch_bounds__(64 * kVictimBlockWaves) void kbg_victim_why_kernel(VictimWhyArgs a, VictimTables t) {
+  __shared__ uint32_t s_out[kVictimWhyOut];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  if (threadIdx.x < kVictimWhyOut)
+    s_out[threadIdx.x] = threadIdx.x >= kWhyCauses && threadIdx.x < 2 * kWhyCauses ? 0xffffffffu : 0u;
+  __syncthreads();
+  const VictimScan& p = a.q[blockIdx.y];
+  const int row = blockIdx.x * kVictimNodesPerBlock + w;
+  if (row < a.node_n) {
+    const uint32_t key = victim_why_node<2>(a, p, t, row, lane);  // wave-uniform
+    if (key != 0xffffffffu && lane == 0) {
+      const uint32_t cause = key & 0xffu;
+      atomicAdd(&s_out[cause], 1u);
+      atomicMin(&s_out[kWhyCauses + cause], (uint32_t)(a.node_lo + row));
+      for (int f = 0; f < 3; ++f)
+        if ((key >> (8 + f)) & 1u) atomicAdd(&s_out[2 * kWhyCauses + f], 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kVictimWhyOut) {
+    const int k = threadIdx.x;
+    const uint32_t v = s_out[k];
+    uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + (size_t)blockIdx.y * kVictimWhyOut + k;
+    if (k >= kWhyCauses && k < 2 * kWhyCauses) {
+      if (v != 0xffffffffu) atomicMin(o, v);
+    } else if (v) {
+      atomicAdd(o, v);
+    }
+  }
+}
+
+// One wave per (big row, query), four to a workgroup, chunk masks in LDS as in
+// kbg_victim_big_kernel; lane 0 adds the node to the query's row.
+__global__ __launch_bounds__(256) void kbg_victim_why_big_kernel(VictimWhyArgs a, VictimTables t,
+                                                                 const int32_t* __restrict__ rows, int32_t n_rows) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_rows) return;
+  __shared__ uint64_t s_masks[4][3 * kVictimChunks];
+  const VictimScan& p = a.q[blockIdx.y];
+  const int row = rows[i];
+  const uint32_t key = victim_why_node<kVictimChunks>(a, p, t, row, lane, s_masks[threadIdx.x >> 6]);
+  if (key == 0xffffffffu || lane != 0) return;
+  const uint32_t cause = key & 0xffu;
+  uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + (size_t)blockIdx.y * kVictimWhyOut;
+  atomicAdd(o + cause, 1u);
+  atomicMin(o + kWhyCauses + cause, (uint32_t)(a.node_lo + row));
+  for (int f = 0; f < 3; ++f)
+    if ((key >> (8 + f)) & 1u) atomicAdd(o + 2 * kWhyCauses + f, 1u);
+}
+
+hipError_t launch_victim_why(const VictimWhyArgs& a, const VictimTables& t, hipStream_t stream, hipEvent_t start,
+                             hipEvent_t stop) {
+  if (a.nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kbg_victim_why_init_kernel, dim3((a.nq * kVictimWhyOut + 255) / 256), dim3(256), 0, stream, a.out,
+                     a.nq);
+  if (a.node_n <= 0) return hipGetLastError();
+  hipExtLaunchKernelGGL(kbg_victim_why_kernel,
+                        dim3((a.node_n + kVictimNodesPerBlock - 1) / kVictimNodesPerBlock, a.nq),
+                        dim3(64 * kVictimBlockWaves), 0, stream, start, stop, 0, a, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, const int32_t* rows, int32_t n_rows,
+                                 hipStream_t stream) {
+  if (n_rows <= 0 || a.nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kbg_victim_why_big_kernel, dim3((n_rows + 3) / 4, a.nq), dim3(256), 0, stream, a, t, rows, n_rows);
+  return hipGetLastError();
+}
+
 __device__ __forceinline__ void apply_node_delta(const NodeSoA& nd, const NodeDelta& x) {
   nd.idle_cpu[x.node] = x.idle[0];
   nd.idle_mem[x.node] = x.idle[1];

@@ -770,6 +770,9 @@ void free_device(Session& S) {
   S.why_out_cap = 0;
   S.d_stage = nullptr;  // (one of d_allocs)
   S.stage_valid = false;
+  S.d_vwhy_q = nullptr;  // (d_allocs too)
+  S.d_vwhy_out = nullptr;
+  S.vwhy_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1420,6 +1423,18 @@ kbg_status kbg_job_reasons_get(kbg_session* s, int32_t job, kbg_job_reasons* out
   if (S.cycle_started && S.committed_ready[job] < S.jobs_in[job].min_available && (size_t)job < S.reasons.size())
     *out = S.reasons[job];
   return KBG_OK;
+}
+
+kbg_status kbg_victim_reasons(kbg_session* s, int32_t mode, const int32_t* jobs, int32_t n_jobs, kbg_victim_why* out) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return victim_reasons(s->s, mode, jobs, n_jobs, out);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
 }
 
 kbg_status kbg_queue_state_get(kbg_session* s, int32_t queue, kbg_queue_state* out) {

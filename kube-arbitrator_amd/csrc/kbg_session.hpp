@@ -564,6 +564,10 @@ struct Session {
   uint8_t* h_vbig_dev = nullptr;
   size_t h_vbig_cap = 0;
   int32_t* d_big_rows = nullptr;
+  // kbg_victim_reasons: the staged queries and their result rows (HBM, grown on demand)
+  kbg::VictimScan* d_vwhy_q = nullptr;
+  int32_t* d_vwhy_out = nullptr;
+  size_t vwhy_cap = 0;                                // queries both hold
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while

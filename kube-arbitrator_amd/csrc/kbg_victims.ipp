@@ -1072,3 +1072,263 @@ kbg_status preempt_cycle(Session& S, kbg_decision* out, int32_t cap, int32_t* n_
   vprof().print("preempt", S.stats.preempt_ms);
   return copy_log(S, out, cap, n_out, result);
 }
+
+// =========================================================== victim reasons
+// kbg_victim_reasons: why the next reclaim / preempt try of a job's first
+// Pending task would find no victims, node by node, against the session as it
+// is now. The cause of each live node is the first that applies in the
+// reference's order (kbg_device.hpp VictimWhy); nothing of the session changes.
+
+// host_stop restated with the cause and each fn's own result: the cause of
+// node n for task t in the low byte and, for NO_VICTIMS, the fns of a walked
+// tier that keep nobody of the whole preemptee list (VictimPlugin bits) from
+// bit 8. The predicate stage follows compute_fit_deltas' stage_of with the
+// current pod counts, ports and affinity state. The node is live.
+uint32_t host_why(Session& S, const kbg::StagePlanes& sp, int32_t mode, int32_t t, int32_t n) {
+  const int32_t cls = S.task_class[t];
+  if (S.panic_node[n]) return KBG_VWHY_PANIC;  // predicates.go:122-123
+  if (S.pred_active) {
+    const size_t w = (size_t)cls * S.W + (n >> 6);
+    const uint64_t bit = 1ull << (n & 63);
+    if (S.ntasks[n] >= S.maxtasks[n]) return KBG_WHY_POD_CAP;
+    if (!(sp.sel_ok[w] & bit)) return KBG_WHY_SELECTOR;
+    if (S.has_ports)
+      for (int32_t pw = 0; pw < S.PW; ++pw)
+        if (S.node_ports[(size_t)n * S.PW + pw] & S.cls_conf[(size_t)cls * S.PW + pw]) return KBG_WHY_HOST_PORTS;
+    if (sp.unsched[n >> 6] & bit) return KBG_WHY_UNSCHEDULABLE;
+    if (!(sp.taint_ok[w] & bit)) return KBG_WHY_TAINTS;
+    if (S.has_aff && !kbg::aff_ok(S, S.affm->st, cls, n)) return KBG_WHY_POD_AFFINITY;
+  }
+  const int32_t pj = S.task_job[t], pq = S.job_queue[pj];
+  std::vector<int32_t> pre;
+  for (int32_t k = S.nt_off[n]; k < S.nt_off[n + 1]; ++k) {
+    const int32_t v = S.nt_task[k];
+    if (!S.trun[v]) continue;
+    const int32_t jv = S.task_job[v];
+    bool f;
+    if (mode == kbg::VM_PREEMPT_JOBS) f = S.job_queue[jv] == pq && jv != pj;
+    else if (mode == kbg::VM_PREEMPT_TASKS) f = jv == pj;
+    else f = S.job_queue[jv] != pq;
+    if (f) pre.push_back(v);
+  }
+  if (pre.empty()) return KBG_VWHY_NO_PREEMPTEES;
+  const std::vector<int32_t>& tiers = mode == kbg::VM_RECLAIM ? S.tier_reclaim : S.tier_preempt;
+  std::vector<char> kg, kd, kp;
+  std::vector<std::pair<int32_t, Res>> alloc;
+  auto entry = [&](int32_t id, const Res& init) -> Res& {
+    for (auto& e : alloc)
+      if (e.first == id) return e.second;
+    alloc.emplace_back(id, init);
+    return alloc.back().second;
+  };
+  auto any = [](const std::vector<char>& k) { return std::find(k.begin(), k.end(), 1) != k.end(); };
+  uint32_t empty = 0;
+  for (int32_t fns : tiers) {
+    kg.assign(pre.size(), 1);
+    kd.assign(pre.size(), 1);
+    kp.assign(pre.size(), 1);
+    if (fns & kbg::VP_GANG)  // gang.go:104-124
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t jv = S.task_job[pre[i]];
+        kg[i] = S.jobs_in[jv].min_available <= S.committed_ready[jv] - 1;
+      }
+    if (fns & kbg::VP_DRF) {  // drf.go:80-105
+      Res la = S.fin.jalloc[pj];
+      kbg::res_add(la, S.treq[t]);
+      const double ls = share_of(la, S.drf_total);
+      alloc.clear();
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t jv = S.task_job[pre[i]];
+        Res& a = entry(jv, S.fin.jalloc[jv]);
+        if (!kbg::res_sub(a, S.treq[pre[i]])) return KBG_VWHY_PANIC;
+        const double rs = share_of(a, S.drf_total);
+        kd[i] = ls < rs || std::fabs(ls - rs) <= 0.000001;
+      }
+    }
+    if (fns & kbg::VP_PROP) {  // proportion.go:161-186
+      alloc.clear();
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t q = S.job_queue[S.task_job[pre[i]]];
+        const Res& r = S.treq[pre[i]];
+        Res& a = entry(q, S.fin.qalloc[q]);
+        if (a.c < r.c && a.m < r.m && a.g < r.g) {  // Resource.Less: skipped
+          kp[i] = 0;
+          continue;
+        }
+        if (!kbg::res_sub(a, r)) return KBG_VWHY_PANIC;
+        kp[i] = kbg::res_le(S.q_deserved[q], a);
+      }
+    }
+    if ((fns & kbg::VP_GANG) && !any(kg)) empty |= kbg::VP_GANG;
+    if ((fns & kbg::VP_DRF) && !any(kd)) empty |= kbg::VP_DRF;
+    if ((fns & kbg::VP_PROP) && !any(kp)) empty |= kbg::VP_PROP;
+    Res all{};
+    bool some = false;
+    for (size_t i = 0; i < pre.size(); ++i)
+      if (kg[i] && kd[i] && kp[i]) {
+        some = true;
+        kbg::res_add(all, S.treq[pre[i]]);  // validateVictims (preempt.go:242-253)
+      }
+    if (!some) continue;
+    const Res& req = S.treq[t];
+    return (all.c < req.c && all.m < req.m && all.g < req.g) ? KBG_VWHY_NOT_ENOUGH : KBG_VWHY_VICTIMS;
+  }
+  return KBG_VWHY_NO_VICTIMS | (empty << 8);
+}
+
+kbg_status victim_reasons(Session& S, int32_t mode, const int32_t* jobs, int32_t n_jobs, kbg_victim_why* out) {
+  if (!S.opts.reasons) return fail(KBG_E_INVALID, "the session was opened without kbg_options.reasons");
+  if (S.comm) return fail(KBG_E_UNSUPPORTED, "victim reasons on a session over a communicator");
+  if (!S.stream) return fail(KBG_E_UNSUPPORTED, "victim reasons on a session without a device");
+  if (!S.cycle_started) return fail(KBG_E_INVALID, "victim reasons before the cycle's first action");
+  if (mode < kbg::VM_PREEMPT_JOBS || mode > kbg::VM_RECLAIM) return fail(KBG_E_INVALID, "victim mode");
+  if (n_jobs < 0 || (n_jobs > 0 && !out)) return fail(KBG_E_INVALID, "null argument");
+  if (!jobs && n_jobs != S.n_jobs)
+    return fail(KBG_E_INVALID, "jobs == NULL describes every job: n_jobs must be the job count");
+  for (int32_t i = 0; jobs && i < n_jobs; ++i)
+    if (jobs[i] < 0 || jobs[i] >= S.n_jobs) return fail(KBG_E_INVALID, "job index");
+  if (n_jobs == 0) return KBG_OK;
+  const std::vector<int32_t>& tiers = mode == kbg::VM_RECLAIM ? S.tier_reclaim : S.tier_preempt;
+  int32_t all_fns = 0;
+  for (int32_t f : tiers) all_fns |= f;
+
+  // one query per distinct key; a job's row is its key's
+  struct Query {
+    kbg::VictimScan p;
+    int32_t task;
+  };
+  std::vector<Query> qs;
+  std::vector<int32_t> q_of(n_jobs, -1);
+  std::map<std::tuple<int32_t, int32_t, int32_t, double, double, double, double>, int32_t> seen;
+  const auto pending = pending_by_job(S);
+  std::vector<char> job_cands(S.n_jobs, 0);  // the job holds a victim candidate (a task Running at open)
+  for (int32_t t : S.nt_task) job_cands[S.task_job[t]] = 1;
+  for (int32_t i = 0; i < n_jobs; ++i) {
+    const int32_t pj = jobs ? jobs[i] : i;
+    kbg_victim_why& o = out[i];
+    o = kbg_victim_why{};
+    if (pending[pj].empty()) continue;
+    const int32_t t = pending[pj][0];
+    o.valid = 1;
+    o.task = t;
+    const int32_t q = S.job_queue[pj];
+    if (mode == kbg::VM_RECLAIM)  // reclaim.go:88
+      o.queue_overused = S.has_prop && S.q_has_attr[q] && kbg::res_le(S.q_deserved[q], S.fin.qalloc[q]) ? 1 : 0;
+    kbg::VictimScan p{};
+    p.n_nodes = S.n_nodes;
+    p.node_lo = S.tab_lo;
+    p.node_n = S.tab_n;
+    p.W = S.W;
+    p.cls = S.task_class[t];
+    p.cap_check = S.pred_active ? 1 : 0;
+    p.mode = mode;
+    p.n_tiers = (int32_t)tiers.size();
+    for (int32_t k = 0; k < p.n_tiers; ++k) p.tier_fns[k] = tiers[k];
+    p.job = pj;
+    p.queue = q;
+    p.req[0] = S.treq[t].c;
+    p.req[1] = S.treq[t].m;
+    p.req[2] = S.treq[t].g;
+    Res la = S.fin.jalloc[pj];
+    kbg::res_add(la, S.treq[t]);
+    p.ls = share_of(la, S.drf_total);
+    // try_task's VictimKey rule: the job enters the preemptee filter only through its tasks Running at
+    // open, and only under the preempt modes (reclaim filters by queue alone); ls matters only to a drf fn
+    const int32_t kjob = mode != kbg::VM_RECLAIM && job_cands[pj] ? pj : -1;
+    const auto key = std::make_tuple(kjob, p.cls, p.queue, p.req[0], p.req[1], p.req[2],
+                                     (all_fns & kbg::VP_DRF) ? p.ls : 0.0);
+    auto [it, fresh] = seen.emplace(key, (int32_t)qs.size());
+    if (fresh) qs.push_back(Query{p, t});
+    q_of[i] = it->second;
+  }
+  const int32_t Q = (int32_t)qs.size();
+  if (Q == 0) return KBG_OK;
+  if (kbg_status st = ensure_stage_planes(S); st != KBG_OK) return st;
+  const kbg::StagePlanes hp = kbg::kbg_stage_planes(S.h_stage.data(), S.n_classes, S.W);
+  std::vector<int32_t> rows((size_t)Q * kbg::kVictimWhyOut, 0);
+  for (int32_t i = 0; i < Q; ++i)
+    std::fill_n(rows.begin() + (size_t)i * kbg::kVictimWhyOut + kbg::kWhyCauses, kbg::kWhyCauses, -1);
+  auto host_add = [&](int32_t i, int32_t n) {
+    if (!((hp.live[n >> 6] >> (n & 63)) & 1ull)) return;
+    const uint32_t key = host_why(S, hp, mode, qs[i].task, n);
+    int32_t* r = rows.data() + (size_t)i * kbg::kVictimWhyOut;
+    const int32_t c = (int32_t)(key & 0xffu);
+    r[c]++;
+    int32_t& first = r[kbg::kWhyCauses + c];
+    if (first < 0 || n < first) first = n;
+    for (int f = 0; f < 3; ++f)
+      if ((key >> (8 + f)) & 1u) r[2 * kbg::kWhyCauses + f]++;
+  };
+  // The device names the stage from the static planes alone; with host ports,
+  // pod affinity or a nil Node the folded class bit cannot: the whole table on
+  // the host. KBG_HOST_VICTIM_WHY, read per call, asks for that on any session
+  // (A/B parity tests, as KBG_HOST_FITDELTA).
+  const bool host_only = S.has_ports || S.has_aff || S.any_nil || getenv("KBG_HOST_VICTIM_WHY") != nullptr;
+  if (host_only) {
+    for (int32_t i = 0; i < Q; ++i)
+      for (int32_t n = 0; n < S.n_nodes; ++n) host_add(i, n);
+  } else {
+    const std::vector<int32_t> jready = S.fin.jready;  // (vt_setup aligns it for the actions' job order keys)
+    kbg_status st = vt_setup(S);
+    S.fin.jready = jready;
+    if (st != KBG_OK) return st;
+    if (!S.sdeltas.empty() || !S.mask_dirty.empty())
+      if ((st = victim_push(S, std::vector<int32_t>{})) != KBG_OK) return st;
+    constexpr int32_t kChunk = 32768;  // queries per launch (the grid's second dimension)
+    const size_t cap = (size_t)std::min(Q, kChunk);
+    if (S.vwhy_cap < cap) {
+      for (void* p : {(void*)S.d_vwhy_q, (void*)S.d_vwhy_out})
+        if (p) {
+          pool_put(p);
+          S.d_allocs.erase(std::find(S.d_allocs.begin(), S.d_allocs.end(), p));
+        }
+      S.d_vwhy_q = nullptr;
+      S.d_vwhy_out = nullptr;
+      S.vwhy_cap = 0;
+      if ((st = dalloc(S, &S.d_vwhy_q, cap)) != KBG_OK) return st;
+      if ((st = dalloc(S, &S.d_vwhy_out, cap * kbg::kVictimWhyOut)) != KBG_OK) return st;
+      S.vwhy_cap = cap;
+    }
+    const kbg::StagePlanes dp = kbg::kbg_stage_planes(S.d_stage, S.n_classes, S.W);
+    std::vector<kbg::VictimScan> stage(cap);
+    double why_ms = 0;  // event time of the kbg_victim_why_kernel launches
+    for (int32_t q0 = 0; q0 < Q; q0 += kChunk) {
+      const int32_t nq = std::min(kChunk, Q - q0);
+      for (int32_t i = 0; i < nq; ++i) stage[i] = qs[q0 + i].p;
+      HIP_TRY(hipMemcpyAsync(S.d_vwhy_q, stage.data(), (size_t)nq * sizeof(kbg::VictimScan), hipMemcpyHostToDevice,
+                             S.stream));
+      const kbg::VictimWhyArgs a{S.d_vwhy_q, nq,         S.n_nodes,  S.W,     S.tab_lo,    S.tab_n,
+                                 dp.sel_ok,  dp.taint_ok, dp.unsched, dp.live, S.d_vwhy_out};
+      HIP_TRY(kbg::launch_victim_why(a, S.vt, S.stream, S.ev[0], S.ev[1]));
+      if (!S.big_rows.empty())
+        HIP_TRY(kbg::launch_victim_why_big(a, S.vt, S.d_big_rows, (int32_t)S.big_rows.size(), S.stream));
+      HIP_TRY(hipMemcpyAsync(rows.data() + (size_t)q0 * kbg::kVictimWhyOut, S.d_vwhy_out,
+                             (size_t)nq * kbg::kVictimWhyOut * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
+      HIP_TRY(hipStreamSynchronize(S.stream));  // (the staging vector is rewritten by the next chunk)
+      if (S.tab_n > 0) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        why_ms += ms;
+      }
+    }
+    S.vstage_busy = false;
+    for (int32_t i = 0; i < Q; ++i)  // nodes past kMaxNodeCandidates are in neither kernel
+      for (int32_t n : S.huge_nodes) host_add(i, n);
+    if (getenv("KBG_PROFILE_VICTIM"))
+      fprintf(stderr, "[kbg victim] reasons mode %d: %d jobs, %d keys, why kernel %.3f ms (%.3f ms per key)\n", mode,
+              n_jobs, Q, why_ms, why_ms / Q);
+  }
+  S.vc.valid = false;  // (as the actions do on entry)
+  for (int32_t i = 0; i < n_jobs; ++i) {
+    if (q_of[i] < 0) continue;
+    const int32_t* r = rows.data() + (size_t)q_of[i] * kbg::kVictimWhyOut;
+    kbg_victim_why& o = out[i];
+    for (int c = 0; c < KBG_VWHY_COUNT; ++c) {
+      o.count[c] = r[c];
+      o.first_node[c] = r[kbg::kWhyCauses + c];
+      o.visited += r[c];
+    }
+    for (int f = 0; f < 3; ++f) o.fn_empty[f] = r[2 * kbg::kWhyCauses + f];
+  }
+  return KBG_OK;
+}

@@ -167,6 +167,16 @@ class kbg_job_reasons(ctypes.Structure):
                 ("first_node", i32 * 6), ("reserved", i32 * 2)]
 
 
+# kbg_victim_reasons: the mode, and the causes after the six WHY_* stages
+VMODE_PREEMPT_JOBS, VMODE_PREEMPT_TASKS, VMODE_RECLAIM = range(3)
+VWHY_NO_PREEMPTEES, VWHY_NO_VICTIMS, VWHY_NOT_ENOUGH, VWHY_VICTIMS, VWHY_PANIC, VWHY_COUNT = range(6, 12)
+
+
+class kbg_victim_why(ctypes.Structure):
+    _fields_ = [("valid", i32), ("task", i32), ("visited", i32), ("queue_overused", i32), ("count", i32 * 11),
+                ("first_node", i32 * 11), ("fn_empty", i32 * 3), ("reserved", i32 * 3)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -257,6 +267,7 @@ SIGNATURES = {
     "kbg_job_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_state)]),
     "kbg_queue_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_queue_state)]),
     "kbg_job_reasons_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_reasons)]),
+    "kbg_victim_reasons": (i32, [ctypes.c_void_p, i32, P(i32), i32, P(kbg_victim_why)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -579,6 +579,20 @@ class Session:
         _abi.check(_abi.lib().kbg_job_reasons_get(self.handle, j, ctypes.byref(st)))
         return st
 
+    def victim_reasons(self, mode, jobs=None):
+        """kbg_victim_why per job (every job, or the indices `jobs`): why the
+        next reclaim / preempt try of its first Pending task would find no
+        victims, against the session as it is now. Legal after the cycle's
+        first action on sessions opened with reasons=True; changes nothing."""
+        if jobs is None:
+            n, arr = len(self.jobs), None
+        else:
+            n = len(jobs)
+            arr = (ctypes.c_int32 * max(n, 1))(*jobs)
+        out = (_abi.kbg_victim_why * max(n, 1))()
+        _abi.check(_abi.lib().kbg_victim_reasons(self.handle, int(mode), arr, n, out))
+        return list(out[:n])
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))

@@ -7,7 +7,9 @@
 // copies its argument struct when it is called, as a kernel launch does;
 // memory the arguments point to is read when the operation runs.
 // tests/test_hostsim_kernels.py holds them to the references the GPU kernels
-// are held to (tests/kernel_ref.py, tests/victim_ref.py).
+// are held to (tests/kernel_ref.py, tests/victim_ref.py);
+// tests/test_hostsim_victim_why.py does so for the victim-reasons launchers
+// (tests/victim_why_ref.py).
 //
 // The victim launchers count their launches (kbg_hostsim_launch_counts, an
 // export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
@@ -465,6 +467,115 @@ void victim_big_run(const VictimScan& p, const VictimTables& t, const int32_t* r
   }
 }
 
+// ---- victim reasons (kbg_device.hpp VictimWhy): the cause of table row `row`
+// for query p, per node, and the fns of a walked tier whose own result over
+// the whole preemptee list is empty (VictimPlugin bits in *fn_empty, set for
+// kWhyNoVictims only). The node is live.
+int32_t victim_why_cause(const VictimWhyArgs& a, const VictimScan& p, const VictimTables& t, int32_t row,
+                         int32_t* fn_empty) {
+  *fn_empty = 0;
+  const int32_t n = a.node_lo + row;
+  const uint64_t bit = 1ull << (n & 63);
+  if (t.panic_node[n]) return kWhyPanic;  // predicates.go:122-123
+  if (p.cap_check) {                      // :125-183, the first failing stage
+    if (t.ntasks[row] >= t.maxtasks[row]) return 0;
+    if (!(a.sel_ok[(size_t)p.cls * a.W + (n >> 6)] & bit)) return 1;
+    if (a.unsched[n >> 6] & bit) return 3;
+    if (!(a.taint_ok[(size_t)p.cls * a.W + (n >> 6)] & bit)) return 4;
+  }
+  const int32_t* jq = reinterpret_cast<const int32_t*>(t.c_jq);
+  std::vector<size_t> pre;
+  for (size_t pos = (size_t)t.nt_off[n]; pos < (size_t)t.nt_off[n + 1]; ++pos) {
+    if (!t.c_run[pos]) continue;
+    const int32_t job = jq[2 * pos], queue = jq[2 * pos + 1];
+    bool f;
+    if (p.mode == VM_PREEMPT_JOBS) f = queue == p.queue && job != p.job;
+    else if (p.mode == VM_PREEMPT_TASKS) f = job == p.job;
+    else f = queue != p.queue;
+    if (f) pre.push_back(pos);
+  }
+  if (pre.empty()) return kWhyNoPreemptees;
+  int32_t empty = 0;
+  for (int32_t ti = 0; ti < p.n_tiers; ++ti) {
+    const int32_t fns = p.tier_fns[ti];
+    std::vector<char> kg(pre.size(), 1), kd(pre.size(), 1), kp(pre.size(), 1);
+    if (fns & VP_GANG)
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t job = jq[2 * pre[i]];
+        kg[i] = t.j_min[job] <= t.j_ready[job] - 1;
+      }
+    if (fns & VP_DRF) {
+      std::map<int32_t, Alloc3> alloc;
+      for (size_t i = 0; i < pre.size(); ++i) {
+        double* al = running(alloc, jq[2 * pre[i]], t.j_alloc);
+        if (!sub3(al, t.c_req + 3 * pre[i])) return kWhyPanic;
+        const double rs = share3(al, t.drf_total);
+        kd[i] = p.ls < rs || std::fabs(p.ls - rs) <= 0.000001;
+      }
+    }
+    if (fns & VP_PROP) {
+      std::map<int32_t, Alloc3> alloc;
+      for (size_t i = 0; i < pre.size(); ++i) {
+        const int32_t queue = jq[2 * pre[i] + 1];
+        const double* r = t.c_req + 3 * pre[i];
+        double* al = running(alloc, queue, t.q_alloc);
+        if (less3(al, r)) {  // skipped: the allocation stays
+          kp[i] = 0;
+          continue;
+        }
+        if (!sub3(al, r)) return kWhyPanic;
+        kp[i] = le3(t.q_deserved + 3 * (size_t)queue, al);
+      }
+    }
+    auto none = [](const std::vector<char>& k) { return std::find(k.begin(), k.end(), 1) == k.end(); };
+    if ((fns & VP_GANG) && none(kg)) empty |= VP_GANG;
+    if ((fns & VP_DRF) && none(kd)) empty |= VP_DRF;
+    if ((fns & VP_PROP) && none(kp)) empty |= VP_PROP;
+    double all[3] = {0.0, 0.0, 0.0};  // validateVictims, in victims order
+    bool some = false;
+    for (size_t i = 0; i < pre.size(); ++i)
+      if (kg[i] && kd[i] && kp[i]) {
+        some = true;
+        for (int d = 0; d < 3; ++d) all[d] += t.c_req[3 * pre[i] + d];
+      }
+    if (some) return less3(all, p.req) ? kWhyNotEnough : kWhyVictims;
+  }
+  *fn_empty = empty;
+  return kWhyNoVictims;
+}
+
+void victim_why_add(const VictimWhyArgs& a, const VictimTables& t, int32_t q, int32_t row) {
+  const int32_t n = a.node_lo + row;
+  if (!((a.live[n >> 6] >> (n & 63)) & 1ull)) return;
+  int32_t fn_empty = 0;
+  const int32_t c = victim_why_cause(a, a.q[q], t, row, &fn_empty);
+  int32_t* o = a.out + (size_t)q * kVictimWhyOut;
+  o[c]++;
+  if (o[kWhyCauses + c] < 0 || n < o[kWhyCauses + c]) o[kWhyCauses + c] = n;
+  for (int f = 0; f < 3; ++f)
+    if ((fn_empty >> f) & 1) o[2 * kWhyCauses + f]++;
+}
+
+// Every row gets its empty value, then the live nodes of up to 128 candidates.
+void victim_why_run(const VictimWhyArgs& a, const VictimTables& t) {
+  for (int32_t q = 0; q < a.nq; ++q) {
+    int32_t* o = a.out + (size_t)q * kVictimWhyOut;
+    std::fill(o, o + kVictimWhyOut, 0);
+    std::fill(o + kWhyCauses, o + 2 * kWhyCauses, -1);
+    for (int32_t row = 0; row < a.node_n; ++row)
+      if (t.nt_off[a.node_lo + row + 1] - t.nt_off[a.node_lo + row] <= 128) victim_why_add(a, t, q, row);
+  }
+}
+
+// The listed rows of 129..kMaxNodeCandidates candidates, added to the rows.
+void victim_why_big_run(const VictimWhyArgs& a, const VictimTables& t, const int32_t* rows, int32_t n_rows) {
+  for (int32_t q = 0; q < a.nq; ++q)
+    for (int32_t i = 0; i < n_rows; ++i) {
+      const int32_t L = t.nt_off[a.node_lo + rows[i] + 1] - t.nt_off[a.node_lo + rows[i]];
+      if (L > 128 && L <= kMaxNodeCandidates) victim_why_add(a, t, q, rows[i]);
+    }
+}
+
 void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
   n.idle_cpu[d.node] = d.idle[0];
   n.idle_mem[d.node] = d.idle[1];
@@ -657,6 +768,19 @@ hipError_t launch_victim_prep_inline(const NodeSoA& n, const VictimTables& t, co
   return launch(stream, nullptr, nullptr, [n, t, nd = std::move(nd), sd = std::move(sd)] {
     victim_prep_run(n, t, nd.data(), (int32_t)nd.size(), sd.data(), (int32_t)sd.size());
   });
+}
+
+// (not counted: the launch counters describe the actions' own launches)
+hipError_t launch_victim_why(const VictimWhyArgs& a, const VictimTables& t, hipStream_t stream, hipEvent_t start,
+                             hipEvent_t stop) {
+  if (a.nq <= 0) return hipSuccess;
+  return launch(stream, start, stop, [a, t] { victim_why_run(a, t); });
+}
+
+hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, const int32_t* rows, int32_t n_rows,
+                                 hipStream_t stream) {
+  if (n_rows <= 0 || a.nq <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [a, t, rows, n_rows] { victim_why_big_run(a, t, rows, n_rows); });
 }
 
 }  // namespace kbg

@@ -5,7 +5,7 @@
 //
 //   hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions a,b,...]
 //                [--batch-tasks N] [--candidates N] [--full-scan]
-//                [--general-scan] [--repeat N]
+//                [--general-scan] [--repeat N] [--victim-reasons]
 //
 // Each repeat opens a session, runs the actions (reclaim, allocate, backfill,
 // preempt, in the order given), resets the session, runs them again and
@@ -13,6 +13,10 @@
 // the decision log (Allocate and Pipeline decisions) with the action behind
 // each decision, the eviction log and every node's state as raw bytes, so two
 // builds (or two schedules) are compared with cmp.
+// --victim-reasons opens the session with kbg_options.reasons and calls
+// kbg_victim_reasons for every job in all three modes after reclaim and after
+// preempt. The rows do not go to OUT (the call changes nothing, so OUT is the
+// same file with and without the flag); a summary goes to stderr.
 // Exit status 0 unless the arguments or the files are unusable.
 #include <cstdio>
 #include <cstdlib>
@@ -40,8 +44,32 @@ kbg_status run_action(kbg_session* s, const std::string& a, kbg_decision* out, i
 // Python wrapper makes (kbgpu/actions.py): an action the reference would
 // panic in (KBG_E_REF_PANIC) ends the list, and what the cycle logged up to
 // there is still written.
+// kbg_victim_reasons of every job in the three modes; what it found, to stderr.
+void victim_reasons(kbg_session* s, const std::string& after, int32_t n_jobs) {
+  std::vector<kbg_victim_why> why((size_t)n_jobs + 1);
+  for (int32_t mode = KBG_VMODE_PREEMPT_JOBS; mode <= KBG_VMODE_RECLAIM; ++mode) {
+    const kbg_status st = kbg_victim_reasons(s, mode, nullptr, n_jobs, why.data());
+    if (st != KBG_OK) {
+      fprintf(stderr, "hostsim_main: victim reasons after %s, mode %d: status %d: %s\n", after.c_str(), (int)mode,
+              (int)st, kbg_last_error());
+      continue;
+    }
+    int64_t valid = 0, count[KBG_VWHY_COUNT] = {}, fn[3] = {};
+    for (int32_t j = 0; j < n_jobs; ++j) {
+      if (!why[j].valid) continue;
+      ++valid;
+      for (int c = 0; c < KBG_VWHY_COUNT; ++c) count[c] += why[j].count[c];
+      for (int f = 0; f < 3; ++f) fn[f] += why[j].fn_empty[f];
+    }
+    fprintf(stderr, "hostsim_main: victim reasons after %s, mode %d: %lld jobs with a Pending task; nodes per cause",
+            after.c_str(), (int)mode, (long long)valid);
+    for (int c = 0; c < KBG_VWHY_COUNT; ++c) fprintf(stderr, " %lld", (long long)count[c]);
+    fprintf(stderr, "; fn_empty %lld %lld %lld\n", (long long)fn[0], (long long)fn[1], (long long)fn[2]);
+  }
+}
+
 void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
-                 std::vector<char>& out) {
+                 std::vector<char>& out, int32_t why_jobs = -1) {
   std::vector<kbg_decision> dec((size_t)n_tasks + 1);
   int32_t n = 0;
   for (const std::string& a : actions) {
@@ -52,6 +80,7 @@ void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_
       fprintf(stderr, "hostsim_main: %s: status %d: %s\n", a.c_str(), (int)st, kbg_last_error());
       return;
     }
+    if (why_jobs >= 0 && (a == "reclaim" || a == "preempt")) victim_reasons(s, a, why_jobs);
   }
   // the decision log (Allocate and Pipeline decisions of every action) and the action behind each
   put_i32(out, n);
@@ -80,6 +109,7 @@ int usage() {
   fprintf(stderr,
           "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions reclaim,allocate,backfill,preempt]\n"
           "                    [--batch-tasks N] [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n"
+          "                    [--victim-reasons]\n"
           "  --actions: any of reclaim, allocate, backfill, preempt, run in the order given (default allocate)\n");
   return 2;
 }
@@ -92,6 +122,7 @@ int main(int argc, char** argv) {
   memset(&opts, 0, sizeof opts);
   std::vector<std::string> actions{"allocate"};
   int repeat = 1;
+  bool why = false;
   for (int i = 3; i < argc; ++i) {
     const std::string a = argv[i];
     const bool more = i + 1 < argc;
@@ -118,6 +149,9 @@ int main(int argc, char** argv) {
       opts.full_scan = 1;
     } else if (a == "--general-scan") {
       setenv("KBG_FORCE_GENERAL_SCAN", "1", 1);
+    } else if (a == "--victim-reasons") {
+      why = true;
+      opts.reasons = 1;
     } else if (a == "--repeat" && more) {
       repeat = atoi(argv[++i]);
     } else {
@@ -139,10 +173,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "hostsim_main: open: status %d: %s\n", (int)st, kbg_last_error());
       continue;
     }
-    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out);
+    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1);
     const kbg_status rs = kbg_session_reset(s);
     put_i32(out, (int32_t)rs);
-    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out);
+    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1);
     kbg_session_close(s);
   }
   kbg_snapshot_blob_free(blob);

@@ -5,7 +5,8 @@
 // session and no Grouper: tests/test_kernels_gpu.py builds the inputs and
 // compares the raw device output with a plain reference (tests/kernel_ref.py);
 // tests/test_victim_kernels_gpu.py does so for the victim scan
-// (tests/victim_ref.py).
+// (tests/victim_ref.py), tests/test_victim_why_kernels_gpu.py for the victim
+// reasons (tests/victim_why_ref.py).
 //
 // Output buffers are filled with kProbeSentinel bytes before the launch and
 // are followed by a guard region of kProbeGuardBytes of the same pattern; the
@@ -665,6 +666,121 @@ extern "C" int32_t kbg_tool_probe_victim(const kbg_probe_victim* p, void* nodes,
     PROBE_TRY(hipMemcpy(stop, d_stop, word_bytes, hipMemcpyDeviceToHost));
     PROBE_TRY(hipMemcpy(panic, d_panic, word_bytes, hipMemcpyDeviceToHost));
   }
+  PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(c_run, t.c_run, P, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(j_ready, t.j_ready, J * 4, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(j_alloc, t.j_alloc, 3 * J * 8, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(q_alloc, t.q_alloc, 3 * Q * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// kbg_victim_why_kernel, then kbg_victim_why_big_kernel over the rows of
+// [node_lo, node_lo + node_n) holding 129..kMaxNodeCandidates candidates, as
+// kbg_victim_reasons runs them for nq queries at once.
+struct kbg_probe_victim_why {
+  int32_t n_nodes, W, node_lo, node_n;
+  int32_t stride;   // rows of the node table block (row = node - node_lo)
+  int32_t classes;  // rows of the per-class stage planes
+  int32_t n_cand, n_jobs, n_queues;
+  int32_t nq;       // queries
+  int32_t n_rows;   // the caller's count of big rows; checked against the probe's own
+};
+
+// The flat tables of kbg_tool_probe_victim (no prep; class_mask is not read by
+// these kernels), the stage planes (sel_ok, taint_ok [classes][W], unsched,
+// live [W]) and nq queries (kbg::VictimScan records; n_nodes, W, node_lo and
+// node_n of each must be the probe's). out: nq * kVictimWhyOut words + guard,
+// device memory filled with the sentinel before the launch. The tables the
+// kernels hold through non-const pointers (the node block, c_run, j_ready,
+// j_alloc, q_alloc) are copied back so the caller sees them untouched.
+extern "C" int32_t kbg_tool_probe_victim_why(const kbg_probe_victim_why* p, void* nodes, const uint8_t* panic_node,
+                                             const uint64_t* planes, const int32_t* nt_off, const int32_t* c_jq,
+                                             const double* c_req, uint8_t* c_run, const int32_t* j_min,
+                                             int32_t* j_ready, double* j_alloc, double* q_alloc,
+                                             const double* q_deserved, const double* drf_total,
+                                             const kbg::VictimScan* queries, void* out) {
+  t_error.clear();
+  if (!p || !nodes || !panic_node || !planes || !nt_off || !c_jq || !c_req || !c_run || !j_min || !j_ready ||
+      !j_alloc || !q_alloc || !q_deserved || !drf_total || !queries || !out)
+    return reject("null argument");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->node_lo < 0 || (p->node_lo & 63)) return reject("node_lo not a multiple of 64");
+  if (p->node_n < 1 || (int64_t)p->node_lo + p->node_n > p->n_nodes) return reject("node range outside n_nodes");
+  if (p->stride < 1 || p->node_n > p->stride) return reject("node range outside the table block");
+  if (p->classes < 1) return reject("no class");
+  if (p->n_cand < 0 || p->n_jobs < 1 || p->n_queues < 1) return reject("empty tables");
+  if (p->nq < 1 || p->nq > 65535) return reject("nq outside 1..65535");
+  if (nt_off[0] != 0 || nt_off[p->n_nodes] != p->n_cand) return reject("nt_off does not span the candidates");
+  for (int32_t n = 0; n < p->n_nodes; ++n)
+    if (nt_off[n + 1] < nt_off[n]) return reject("nt_off not increasing");
+  for (int32_t k = 0; k < p->n_cand; ++k)
+    if (c_jq[2 * k] < 0 || c_jq[2 * k] >= p->n_jobs || c_jq[2 * k + 1] < 0 || c_jq[2 * k + 1] >= p->n_queues)
+      return reject("candidate job or queue outside its table");
+  for (int32_t i = 0; i < p->nq; ++i) {
+    const kbg::VictimScan& q = queries[i];
+    if (q.n_nodes != p->n_nodes || q.W != p->W || q.node_lo != p->node_lo || q.node_n != p->node_n)
+      return reject("query: geometry differs from the probe's");
+    if (q.cls < 0 || q.cls >= p->classes) return reject("query: cls outside the planes");
+    if (q.mode < kbg::VM_PREEMPT_JOBS || q.mode > kbg::VM_RECLAIM) return reject("query: mode outside 0..2");
+    if (q.n_tiers < 0 || q.n_tiers > kbg::kMaxVictimTiers) return reject("query: n_tiers outside 0..kMaxVictimTiers");
+    for (int32_t k = 0; k < q.n_tiers; ++k)
+      if (q.tier_fns[k] == 0 || (q.tier_fns[k] & ~(kbg::VP_GANG | kbg::VP_DRF | kbg::VP_PROP)))
+        return reject("query: tier_fns outside the victim fns");
+    if (q.job < 0 || q.job >= p->n_jobs || q.queue < 0 || q.queue >= p->n_queues)
+      return reject("query: job or queue outside its table");
+  }
+  std::vector<int32_t> big_rows;
+  for (int32_t n = p->node_lo; n < p->node_lo + p->node_n; ++n) {
+    const int32_t L = nt_off[n + 1] - nt_off[n];
+    if (L > 128 && L <= kbg::kMaxNodeCandidates) big_rows.push_back(n - p->node_lo);
+  }
+  if (p->n_rows != (int32_t)big_rows.size()) return reject("n_rows is not the number of big rows");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)p->stride, P = (size_t)p->n_cand, J = (size_t)p->n_jobs, Q = (size_t)p->n_queues;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  kbg::VictimTables t{};
+  t.ntasks = (int32_t*)(d + 6 * L);
+  t.maxtasks = (int32_t*)(d + 6 * L) + L;
+  PROBE_TRY(dev_copy(sc, (uint8_t**)&t.panic_node, panic_node, (size_t)p->n_nodes));
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&t.class_mask, (const uint64_t*)nullptr, 2));  // not read by these kernels
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.nt_off, nt_off, (size_t)p->n_nodes + 1));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.c_jq, c_jq, 2 * P));
+  PROBE_TRY(dev_copy(sc, (double**)&t.c_req, c_req, 3 * P));
+  PROBE_TRY(dev_copy(sc, &t.c_run, (const uint8_t*)c_run, P));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.j_queue, (const int32_t*)nullptr, J));  // not read by the kernels
+  PROBE_TRY(dev_copy(sc, (int32_t**)&t.j_min, j_min, J));
+  PROBE_TRY(dev_copy(sc, &t.j_ready, (const int32_t*)j_ready, J));
+  PROBE_TRY(dev_copy(sc, &t.j_alloc, (const double*)j_alloc, 3 * J));
+  PROBE_TRY(dev_copy(sc, &t.q_alloc, (const double*)q_alloc, 3 * Q));
+  PROBE_TRY(dev_copy(sc, (double**)&t.q_deserved, q_deserved, 3 * Q));
+  std::copy(drf_total, drf_total + 3, t.drf_total);
+  int32_t* d_rows = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_rows, big_rows.data(), big_rows.size()));
+  uint64_t* d_planes = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_planes, planes, kbg::kbg_stage_words(p->classes, p->W)));
+  const kbg::StagePlanes sp = kbg::kbg_stage_planes(d_planes, p->classes, p->W);
+
+  kbg::VictimWhyArgs a{};
+  PROBE_TRY(dev_copy(sc, (kbg::VictimScan**)&a.q, queries, (size_t)p->nq));
+  a.nq = p->nq;
+  a.n_nodes = p->n_nodes;
+  a.W = p->W;
+  a.node_lo = p->node_lo;
+  a.node_n = p->node_n;
+  a.sel_ok = sp.sel_ok;
+  a.taint_ok = sp.taint_ok;
+  a.unsched = sp.unsched;
+  a.live = sp.live;
+  const size_t out_bytes = (size_t)p->nq * kbg::kVictimWhyOut * 4 + kProbeGuardBytes;
+  PROBE_TRY(dev_copy(sc, (char**)&a.out, (const char*)nullptr, out_bytes, kProbeSentinel));
+
+  PROBE_TRY(kbg::launch_victim_why(a, t, sc.stream));
+  PROBE_TRY(kbg::launch_victim_why_big(a, t, d_rows, (int32_t)big_rows.size(), sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(c_run, t.c_run, P, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(j_ready, t.j_ready, J * 4, hipMemcpyDeviceToHost));
