@@ -1177,6 +1177,17 @@ kbg_status allocate_cycle(Session& S, kbg_decision* out, int32_t cap, int32_t* n
     }
     rs.rows = mrow.data();
   }
+  // Dead masks (kbg_svc_link.ipp): zeroed every cycle, written at commit.
+  // Off with pod affinity, and KBG_DEAD_MASKS=0 (read per cycle: A/B runs and
+  // the parity tests) runs the walk without them.
+  const bool dead_on = [&] {
+    const char* e = getenv("KBG_DEAD_MASKS");
+    return packed && !S.has_aff && !(e && e[0] == '0');
+  }();
+  if (dead_on) {
+    dead_reset(S);
+    rs.dead = S.dead_mask.data();
+  }
   // The log side of the walk (decision log, gang dispatch, FitError
   // bookkeeping) on a thread of its own, unless host ports or colliding pod
   // keys need the pre-commit port rows (then inline, below).
@@ -1670,6 +1681,7 @@ kbg_status allocate_cycle(Session& S, kbg_decision* out, int32_t cap, int32_t* n
         if (packed) {
           mirror_row(S, mrow[node], node);
           mrow[node].mark = rstamp;
+          if (dead_on) dead_update(S, node);
         }
         const uint64_t c2 = rprof ? cycles() : 0;
         const LogItem it{t, node, kind, true, true, dup, old};

@@ -1143,6 +1143,30 @@ kbg_status derive_host(Session& S, kbg::StaticHost* sh, int* outcome) {
     const int32_t rep = S.shape_task[sh];
     if (rep >= 0 && rep < T) S.shape_req[sh] = S.treq[rep];
   }
+  // request levels of the dead masks, per dimension: the distinct finite
+  // requests in order; more than kDeadLevels of them are thinned to evenly
+  // spaced thresholds from the smallest up (a node dead for a threshold is
+  // dead for every larger request: LessEqual is monotone in the request)
+  for (int d = 0; d < 3; ++d) {
+    auto dim = [d](const Res& r) { return d == 0 ? r.c : d == 1 ? r.m : r.g; };
+    std::vector<double> v;
+    v.reserve(S.shape_req.size());
+    for (const Res& r : S.shape_req)
+      if (std::isfinite(dim(r))) v.push_back(dim(r));
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    std::vector<double>& lv = S.lvl_val[d];
+    lv.clear();
+    const size_t n = v.size(), L = (size_t)Session::kDeadLevels;
+    for (size_t i = 0; i < std::min(n, L); ++i) lv.push_back(n <= L ? v[i] : v[i * n / L]);
+    S.shape_lvl[d].assign(S.shape_req.size(), (uint8_t)Session::kDeadLevels);
+    for (size_t sh = 0; sh < S.shape_req.size(); ++sh) {
+      const double q = dim(S.shape_req[sh]);
+      if (!std::isfinite(q)) continue;  // never masked
+      const size_t k = std::upper_bound(lv.begin(), lv.end(), q) - lv.begin();  // thresholds <= q
+      if (k > 0) S.shape_lvl[d][sh] = (uint8_t)(k - 1);
+    }
+  }
   phase("shapes");
   vwork.join();
   phase("victims join");

@@ -352,6 +352,17 @@ struct Session {
   std::vector<Res> shape_req;                            // each shape's request (the engine reads it by task_shape)
   std::vector<int32_t> shape_task;                       // a candidate task of each shape (-1: none; may be
                                                          // stale: valid while task_shape[it] == the shape)
+  // Request levels of the in-order commit's dead masks: per
+  // dimension (cpu, memory, gpu) the sorted distinct finite requests over
+  // shape_req, thinned to kDeadLevels thresholds, and each shape's level (the
+  // largest threshold <= its request; kDeadLevels: none, never masked).
+  // Built with shape_req (derive_host); the masks themselves are per cycle.
+  static constexpr int32_t kDeadLevels = 32;
+  std::vector<double> lvl_val[3];
+  std::vector<uint8_t> shape_lvl[3];
+  std::vector<uint64_t> dead_mask;                       // [(dim * (kDeadLevels + 1) + level) * W + word]; row
+                                                         // kDeadLevels of a dimension stays zero
+  std::vector<uint8_t> dead_low;                         // [4 * node + dim]: the node's lowest dead level
   std::unordered_map<ShapeKey, int32_t, ShapeHash> shape_ids;  // shape ids, kept across updates
   std::vector<int32_t> shape_of_task;                    // a task's shape once it was a candidate (-1: not yet)
   std::vector<int32_t> pend_dirty_jobs;                  // jobs an update's events touched (their pending lists)

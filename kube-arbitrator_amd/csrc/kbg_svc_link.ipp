@@ -373,6 +373,44 @@ inline void mirror_row(const Session& S, MirrorRow& q, int32_t nd) {
   q.rg = S.rel[nd].g;
   q.nt = S.ntasks[nd];
 }
+// Dead masks of the allocate committer. Per dimension and
+// request level (Session::lvl_val) one W-word mask: bit n is set once the
+// level's value fails Resource.LessEqual in that dimension against node n's
+// Idle and against its Releasing, so no request at or above the level fits
+// the node, whatever its other dimensions. The test is monotone in the
+// request, so a node's dead levels are an up-set and dead_low holds its lowest
+// one. Idle and Releasing only shrink while an allocate runs: a bit set stays
+// right for the rest of the cycle. Under the predicates plugin a node at its
+// pod cap is dead at every level of the first dimension.
+inline size_t dead_row(int d, int32_t level) { return (size_t)d * (Session::kDeadLevels + 1) + (size_t)level; }
+void dead_reset(Session& S) {
+  S.dead_mask.assign(3 * (size_t)(Session::kDeadLevels + 1) * S.W, 0ull);
+  S.dead_low.resize(4 * (size_t)S.n_nodes);
+  for (int32_t n = 0; n < S.n_nodes; ++n)
+    for (int d = 0; d < 3; ++d) S.dead_low[4 * (size_t)n + d] = (uint8_t)S.lvl_val[d].size();
+}
+// after a commit rewrote node nd's Idle, Releasing or pod count
+inline void dead_update(Session& S, int32_t nd) {
+  const double idle[3] = {S.idle[nd].c, S.idle[nd].m, S.idle[nd].g}, rel[3] = {S.rel[nd].c, S.rel[nd].m, S.rel[nd].g};
+  const double kmin[3] = {kbg::kMinMilliCPU, kbg::kMinMemory, kbg::kMinMilliGPU};
+  const bool full = S.pred_active && S.ntasks[nd] >= S.maxtasks[nd];
+  const uint64_t bit = 1ull << (nd & 63);
+  for (int d = 0; d < 3; ++d) {
+    uint8_t& low = S.dead_low[4 * (size_t)nd + d];
+    const double* lv = S.lvl_val[d].data();
+    const double a = idle[d], b = rel[d], mn = kmin[d];
+    int32_t l = low;
+    while (l > 0) {
+      const double r = lv[l - 1];
+      const bool fits = (r < a || __builtin_fabs(a - r) < mn) || (r < b || __builtin_fabs(b - r) < mn);
+      if (fits && !(full && d == 0)) break;
+      --l;
+      S.dead_mask[dead_row(d, l) * S.W + (nd >> 6)] |= bit;
+    }
+    low = (uint8_t)l;
+  }
+}
+
 struct Resolver {
   Session& S;
   std::vector<int32_t>& mark;
@@ -389,6 +427,11 @@ struct Resolver {
   int32_t* floor = nullptr;
   // the committer's packed mirror (nullptr: the separate arrays and `mark`)
   const MirrorRow* rows = nullptr;
+  // the committer's dead masks (nullptr: off; only with `rows`): a listed
+  // node that is dead for the task's shape in some dimension was committed to
+  // after the list's scan (a later scan would not list it), so the walk would
+  // re-check and reject it; it is dropped from the word instead
+  const uint64_t* dead = nullptr;
   void reset(const kbg::Stage& stage) {
     sg = &stage;
     base = stage.base;
@@ -458,9 +501,17 @@ struct Resolver {
                (rm_ < a1 || __builtin_fabs(a1 - rm_) < kbg::kMinMemory) &&
                (rg_ < a2 || __builtin_fabs(a2 - rg_) < kbg::kMinMilliGPU);
       };
+      // The dead masks of the task's shape are looked up at the walk's first
+      // touched candidate: a walk that takes an untouched node first, as most
+      // do while nothing is contended, never pays for them. From there on
+      // every word loses its dead nodes before its bit loop.
+      const bool use_dead = dead && !be;  // (a BestEffort task takes no resource test)
+      const uint64_t *dd0 = nullptr, *dd1 = nullptr, *dd2 = nullptr;
       while (k < end && res < 0) {
         const int32_t w = k >> 6;
         uint64_t bits = m[w].f & (~0ull << (k & 63));
+        bool wmasked = dd0 != nullptr;
+        if (wmasked) bits &= ~(dd0[w] | dd1[w] | dd2[w]);
         const bool wdirty = aff && awm[w] > bs;
         while (bits) {
           const int32_t nd = (w << 6) | __builtin_ctzll(bits);
@@ -479,6 +530,21 @@ struct Resolver {
             *kind = ((m[w].i >> (nd & 63)) & 1ull) ? KBG_KIND_ALLOCATE : KBG_KIND_PIPELINE;
             res = RES_OK;
             break;
+          }
+          if (use_dead && !wmasked) {
+            if (!dd0) {
+              const int32_t shp = S.task_shape[t];
+              dd0 = dead + dead_row(0, S.shape_lvl[0][shp]) * S.W;
+              dd1 = dead + dead_row(1, S.shape_lvl[1][shp]) * S.W;
+              dd2 = dead + dead_row(2, S.shape_lvl[2][shp]) * S.W;
+            }
+            const uint64_t dw = dd0[w] | dd1[w] | dd2[w];
+            bits &= ~dw;
+            wmasked = true;
+            if ((dw >> (nd & 63)) & 1ull) {  // this candidate itself: skipped, not visited
+              --steps;
+              continue;
+            }
           }
           ++rechecks;  // touched since the scan: re-check on the host mirror
           if (cap && q.nt >= q.mt) continue;
