@@ -705,6 +705,50 @@ typedef struct kbg_victim_why {
  * without kbg_options.reasons); KBG_E_UNSUPPORTED over a communicator. The
  * call changes nothing: every later action returns what it would have. */
 kbg_status kbg_victim_reasons(kbg_session* s, int32_t mode, const int32_t* jobs, int32_t n_jobs, kbg_victim_why* out);
+
+/* Why a Pending task would not be placed now (additive within
+ * KBG_ABI_VERSION 13): one row per named task, whether allocate or backfill
+ * ever reached it or not. Every live node of ssn.Nodes is evaluated against
+ * the session as it is NOW (node, job and queue state after the actions run so
+ * far; before the cycle's first action, the snapshot) and goes under exactly
+ * one cause, the first that applies in the order of allocate.go:119-162 and
+ * backfill.go:50-64:
+ *   0..5 KBG_WHY_*               the predicates plugin's first failing stage
+ *                                (predicates.go:125-198); none with the plugin off
+ *   9 KBG_TWHY_PANIC             a nil Node under the predicates plugin (:122-123)
+ *   6 KBG_TWHY_FITS_IDLE         Resreq.LessEqual(node.Idle); a BestEffort task takes
+ *                                no resource test (backfill.go:47-60): every node
+ *                                that passes the stages
+ *   7 KBG_TWHY_FITS_RELEASING    not Idle, but Resreq.LessEqual(node.Releasing)
+ *   8 KBG_TWHY_SHORT             neither
+ * idle_short restates FitError's counts (job_info.go:336-346) over the nodes of
+ * causes 7 and 8: the dimensions in which Idle.FitDelta(Resreq) is negative
+ * (resource_info.go:116-129), so count[7] + count[8] is len(NodesFitDelta) of
+ * an evaluation that visited every node now. */
+enum {
+  KBG_TWHY_FITS_IDLE = 6,
+  KBG_TWHY_FITS_RELEASING = 7,
+  KBG_TWHY_SHORT = 8,
+  KBG_TWHY_PANIC = 9,
+  KBG_TWHY_COUNT = 10
+};
+typedef struct kbg_task_why {
+  int32_t valid;          /* 0: the task is not Pending now; nothing below is set */
+  int32_t task;
+  int32_t visited;        /* live nodes == sum(count) */
+  int32_t best_effort;    /* Resreq.IsEmpty(): backfill's task, no resource test */
+  int32_t queue_overused; /* Overused(queue) holds now: allocate would skip the queue (allocate.go:70-74) */
+  int32_t count[10];
+  int32_t first_node[10]; /* lowest node index per cause, -1 when none */
+  int32_t idle_short[3];  /* over the nodes of causes 7 and 8: Idle.FitDelta(Resreq) negative in cpu, memory, GPU */
+  int32_t reserved[3];
+} kbg_task_why;
+/* out[i] describes tasks[i] (tasks must not be NULL; an index outside the
+ * session's tasks is KBG_E_INVALID, as is a session opened without
+ * kbg_options.reasons). Legal any time after open. KBG_E_UNSUPPORTED over a
+ * communicator or without a device. The call changes nothing: every later
+ * action returns what it would have. */
+kbg_status kbg_task_reasons(kbg_session* s, const int32_t* tasks, int32_t n_tasks, kbg_task_why* out);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

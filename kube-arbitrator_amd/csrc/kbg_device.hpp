@@ -426,4 +426,49 @@ hipError_t launch_victim_why(const VictimWhyArgs& a, const VictimTables& t, hipS
 hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, const int32_t* rows, int32_t n_rows,
                                  hipStream_t stream);
 
+// Why a Pending task would not be placed now (kbg_task_reasons). For each of
+// n_shapes shapes (a static class, the BestEffort flag and a request) every
+// node of the table range [tab_lo, tab_lo + tab_n) whose `live` bit is set goes
+// under exactly one cause, the first that applies (allocate.go:119-162,
+// backfill.go:50-64); a node whose `live` bit is clear, and a bit of the last
+// word at or past tab_lo + tab_n, is counted nowhere whatever the planes hold:
+//   cap_check: ntasks >= maxtasks -> 0 (pod cap), sel_ok clear -> 1,
+//     unsched set -> 3, taint_ok clear -> 4 (KBG_WHY_* codes; cap_check 0: the
+//     predicates plugin is off and none of these occurs);
+//   the shape is BestEffort, or req LessEqual Idle       -> kTwhyFitsIdle;
+//   req LessEqual Releasing                              -> kTwhyFitsReleasing;
+//   otherwise                                            -> kTwhyShort.
+// LessEqual is the reference's `r < a || |a - r| < min` per dimension. Host
+// ports (2), pod affinity (5) and a nil Node (kTwhyPanic) are the host's:
+// sessions holding any take the host path for the whole table.
+// Row s of `out` (kTaskWhyOut words): count[kTwhyCauses], first_node
+// [kTwhyCauses] (lowest global node of the cause, -1 none), idle_short[3]: over
+// the nodes of kTwhyFitsReleasing and kTwhyShort, the dimensions (cpu, memory,
+// GPU) in which Idle.FitDelta(req) is negative, kbg_fitdelta_kernel's
+// expression (a dimension of request 0 subtracts nothing); one word of padding.
+// launch_task_why_init sets every row to its empty value; launch_task_why,
+// after it on the same stream, adds the table's nodes. `out` is device memory:
+// the workgroups add to it with atomics. tab_lo is a multiple of 64.
+enum TaskWhy : int32_t { kTwhyFitsIdle = 6, kTwhyFitsReleasing = 7, kTwhyShort = 8, kTwhyPanic = 9, kTwhyCauses = 10 };
+constexpr int kTaskWhyOut = 2 * kTwhyCauses + 4;
+constexpr int kTaskWhyGroup = 16;  // shapes per workgroup
+constexpr int kTaskWhyWaves = 4;   // 64-node words per workgroup, one per wave
+constexpr int32_t kTaskShapeBestEffort = 1;
+struct TaskShape {
+  int32_t cls;
+  int32_t flags;  // kTaskShapeBestEffort: Resreq.IsEmpty(), no resource test
+  double req[3];
+};
+struct TaskWhyArgs {
+  const double* nodes;  // the node table block (FirstFitArgs.nodes)
+  int32_t stride, W, tab_lo, tab_n;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const TaskShape* shapes;                             // [n_shapes] staged in device memory
+  int32_t n_shapes, cap_check;
+  int32_t* out;  // [n_shapes][kTaskWhyOut]
+};
+hipError_t launch_task_why_init(int32_t* out, int32_t n_shapes, hipStream_t stream);
+hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
+                           hipEvent_t stop = nullptr);
+
 }  // namespace kbg

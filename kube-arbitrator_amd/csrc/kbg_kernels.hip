@@ -1479,6 +1479,120 @@ hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, 
   return hipGetLastError();
 }
 
+// ------------------------------------------------- pending-task reasons
+// kbg_task_reasons: every live node of the table under one cause per shape
+// (kbg_device.hpp TaskWhy). The first-fit walk's geometry with a reduction
+// where that extracts lists: a wave owns one 64-node word, loads its node
+// records once, a lane per node, and keeps them in registers with the word's
+// wave-uniform live and unsched bits; the workgroup's kTaskWhyWaves waves take
+// consecutive words and its kTaskWhyGroup shapes sit in LDS, read as
+// same-address broadcasts. Per shape the causes are disjoint 64-bit masks
+// built on the scalar unit from the class's stage words, the pod-cap ballot
+// and the LessEqual ballots (the reference expression, never the integer
+// shortcut: Releasing and the FitDelta terms are not covered by its proof).
+// Lane k then takes mask k: a popcount and the lowest set bit go to the
+// workgroup's LDS row of the shape. After the barrier one atomic per non-empty
+// slot goes to the shape's global row; the counts are integers and the minima
+// unsigned (the empty value -1 is the largest), so arrival order is nothing.
+// Grid (word blocks, shape groups): C3's 79 words x 302 shapes are 20 x 19
+// workgroups, more than one per CU.
+__global__ __launch_bounds__(256) void kbg_task_why_init_kernel(int32_t* __restrict__ out, int32_t n_shapes) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_shapes * kTaskWhyOut) return;
+  const int k = i % kTaskWhyOut;
+  out[i] = k >= kTwhyCauses && k < 2 * kTwhyCauses ? -1 : 0;
+}
+
+__global__ __launch_bounds__(64 * kTaskWhyWaves) void kbg_task_why_kernel(TaskWhyArgs a) {
+  __shared__ TaskShape s_shape[kTaskWhyGroup];
+  __shared__ uint32_t s_out[kTaskWhyGroup * kTaskWhyOut];
+  constexpr int kShapeWords = sizeof(TaskShape) / 4;
+  const int lane = threadIdx.x & 63;
+  const int s0 = blockIdx.y * kTaskWhyGroup;
+  const int ns = min(kTaskWhyGroup, a.n_shapes - s0);
+  if ((int)threadIdx.x < ns * kShapeWords)
+    reinterpret_cast<uint32_t*>(s_shape)[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.shapes + s0)[threadIdx.x];
+  for (int i = threadIdx.x; i < kTaskWhyGroup * kTaskWhyOut; i += 64 * kTaskWhyWaves) {
+    const int k = i % kTaskWhyOut;
+    s_out[i] = k >= kTwhyCauses && k < 2 * kTwhyCauses ? 0xffffffffu : 0u;
+  }
+  __syncthreads();
+  const int wl = blockIdx.x * kTaskWhyWaves + (int)(threadIdx.x >> 6);  // the wave's word of the table
+  if (wl < ((a.tab_n + 63) >> 6)) {                                     // (wave-uniform)
+    const int w = (a.tab_lo >> 6) + wl;                                 // the global word
+    const int r = min(wl * 64 + lane, a.tab_n - 1);                     // a legal row for the ragged word's lanes
+    const size_t L = (size_t)a.stride;
+    const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * L);
+    const double ic = a.nodes[r], im = a.nodes[L + r], ig = a.nodes[2 * L + r];
+    const double rc = a.nodes[3 * L + r], rm = a.nodes[4 * L + r], rg = a.nodes[5 * L + r];
+    uint64_t valid = a.live[w];
+    if (wl * 64 + 64 > a.tab_n) valid &= (1ull << (a.tab_n - wl * 64)) - 1ull;  // bits past the table's last node
+    const uint64_t capped = a.cap_check ? __ballot(ni[r] >= ni[L + r]) : 0ull;   // predicates.go:125-127
+    const uint64_t uns = a.cap_check ? a.unsched[w] : 0ull;
+    const int code = lane < 2 ? lane : lane < 4 ? lane + 1 : lane + 2;  // lanes 0..6: causes 0, 1, 3, 4, 6, 7, 8
+    for (int s = 0; s < ns; ++s) {
+      const TaskShape& sh = s_shape[s];
+      const uint64_t so = a.cap_check ? a.sel_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+      const uint64_t to = a.cap_check ? a.taint_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+      const double q0 = sh.req[0], q1 = sh.req[1], q2 = sh.req[2];
+      const uint64_t c0 = valid & capped;
+      uint64_t rest = valid & ~capped;
+      const uint64_t c1 = rest & ~so;  // :129-141
+      rest &= so;
+      const uint64_t c3 = rest & uns;  // :157-169
+      rest &= ~uns;
+      const uint64_t c4 = rest & ~to;  // :171-183
+      rest &= to;
+      const uint64_t fi = (sh.flags & kTaskShapeBestEffort) ? ~0ull : fit_mask<false>(ic, im, ig, q0, q1, q2);
+      const uint64_t fr = fit_mask<false>(rc, rm, rg, q0, q1, q2);
+      const uint64_t c6 = rest & fi;
+      rest &= ~fi;  // FitDelta's nodes (allocate.go:127-133): causes 7 and 8
+      const uint64_t c7 = rest & fr, c8 = rest & ~fr;
+      const uint64_t bc = rest & __ballot((q0 > 0 ? ic - (q0 + kMinMilliCPU) : ic) < 0);
+      const uint64_t bm = rest & __ballot((q1 > 0 ? im - (q1 + kMinMemory) : im) < 0);
+      const uint64_t bg = rest & __ballot((q2 > 0 ? ig - (q2 + kMinMilliGPU) : ig) < 0);
+      const uint64_t m = lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c3 : lane == 3 ? c4 : lane == 4 ? c6
+                       : lane == 5 ? c7 : lane == 6 ? c8 : lane == 7 ? bc : lane == 8 ? bm : lane == 9 ? bg : 0ull;
+      if (m) {
+        uint32_t* o = s_out + s * kTaskWhyOut;
+        if (lane < 7) {
+          atomicAdd(o + code, (uint32_t)__popcll(m));
+          atomicMin(o + kTwhyCauses + code, (uint32_t)(w * 64 + __builtin_ctzll(m)));
+        } else {
+          atomicAdd(o + 2 * kTwhyCauses + (lane - 7), (uint32_t)__popcll(m));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ns * kTaskWhyOut; i += 64 * kTaskWhyWaves) {
+    const int k = i % kTaskWhyOut;
+    const uint32_t v = s_out[i];
+    uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + (size_t)s0 * kTaskWhyOut + i;
+    if (k >= kTwhyCauses && k < 2 * kTwhyCauses) {
+      if (v != 0xffffffffu) atomicMin(o, v);
+    } else if (v) {
+      atomicAdd(o, v);
+    }
+  }
+}
+
+hipError_t launch_task_why_init(int32_t* out, int32_t n_shapes, hipStream_t stream) {
+  if (n_shapes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kbg_task_why_init_kernel, dim3((n_shapes * kTaskWhyOut + 255) / 256), dim3(256), 0, stream, out,
+                     n_shapes);
+  return hipGetLastError();
+}
+
+hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
+  const int words = (a.tab_n + 63) >> 6;
+  hipExtLaunchKernelGGL(kbg_task_why_kernel,
+                        dim3((words + kTaskWhyWaves - 1) / kTaskWhyWaves, (a.n_shapes + kTaskWhyGroup - 1) / kTaskWhyGroup),
+                        dim3(64 * kTaskWhyWaves), 0, stream, start, stop, 0, a);
+  return hipGetLastError();
+}
+
 __device__ __forceinline__ void apply_node_delta(const NodeSoA& nd, const NodeDelta& x) {
   nd.idle_cpu[x.node] = x.idle[0];
   nd.idle_mem[x.node] = x.idle[1];

@@ -773,6 +773,9 @@ void free_device(Session& S) {
   S.d_vwhy_q = nullptr;  // (d_allocs too)
   S.d_vwhy_out = nullptr;
   S.vwhy_cap = 0;
+  S.d_twhy_shapes = nullptr;  // (d_allocs too)
+  S.d_twhy_out = nullptr;
+  S.twhy_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1088,6 +1091,8 @@ kbg_status device_scan(Session& S, kbg::Stage& sg, int32_t G, int32_t base) {
 #include "kbg_svc.ipp"  // the scan service: rank 0 and the serving ranks
 
 #include "kbg_victims.ipp"  // preempt / reclaim and their victim scans
+
+#include "kbg_task_why.ipp"  // kbg_task_reasons: why a Pending task would not be placed now
 
 #include "kbg_update.ipp"  // resident session updates (kbg_session_update)
 
@@ -1430,6 +1435,18 @@ kbg_status kbg_victim_reasons(kbg_session* s, int32_t mode, const int32_t* jobs,
   if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
   try {
     return victim_reasons(s->s, mode, jobs, n_jobs, out);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
+}
+
+kbg_status kbg_task_reasons(kbg_session* s, const int32_t* tasks, int32_t n_tasks, kbg_task_why* out) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return task_reasons(s->s, tasks, n_tasks, out);
   } catch (const std::bad_alloc&) {
     return fail(KBG_E_NOMEM, "host allocation failed");
   } catch (const std::exception& e) {

@@ -579,6 +579,10 @@ struct Session {
   kbg::VictimScan* d_vwhy_q = nullptr;
   int32_t* d_vwhy_out = nullptr;
   size_t vwhy_cap = 0;                                // queries both hold
+  // kbg_task_reasons: the staged shapes and their result rows (HBM, grown on demand)
+  kbg::TaskShape* d_twhy_shapes = nullptr;
+  int32_t* d_twhy_out = nullptr;
+  size_t twhy_cap = 0;                                // shapes both hold
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while

@@ -177,6 +177,15 @@ class kbg_victim_why(ctypes.Structure):
                 ("first_node", i32 * 11), ("fn_empty", i32 * 3), ("reserved", i32 * 3)]
 
 
+# kbg_task_reasons: the causes after the six WHY_* stages
+TWHY_FITS_IDLE, TWHY_FITS_RELEASING, TWHY_SHORT, TWHY_PANIC, TWHY_COUNT = range(6, 11)
+
+
+class kbg_task_why(ctypes.Structure):
+    _fields_ = [("valid", i32), ("task", i32), ("visited", i32), ("best_effort", i32), ("queue_overused", i32),
+                ("count", i32 * 10), ("first_node", i32 * 10), ("idle_short", i32 * 3), ("reserved", i32 * 3)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -268,6 +277,7 @@ SIGNATURES = {
     "kbg_queue_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_queue_state)]),
     "kbg_job_reasons_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_reasons)]),
     "kbg_victim_reasons": (i32, [ctypes.c_void_p, i32, P(i32), i32, P(kbg_victim_why)]),
+    "kbg_task_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_task_why)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -77,6 +77,32 @@ def unschedulable_message(reasons, fit=None):
     return f"0/{reasons.visited} nodes are available: {', '.join(parts)}."
 
 
+def pending_message(row):
+    """One line, kube-scheduler style, for a Pending task (a Session.
+    task_reasons row): the nodes that would take it now when there are any,
+    else the live nodes by the predicate stage that turns them away and
+    FitError's resource parts over the nodes that pass every stage but lack
+    Idle resources, each group sorted as unschedulable_message sorts its own."""
+    if not row["valid"]:
+        return "not pending"
+    count, total = row["count"], row["visited"]
+    if total == 0:
+        return "0 nodes are available"
+    fits = count[_abi.TWHY_FITS_IDLE] + count[_abi.TWHY_FITS_RELEASING]
+    tail = " (its queue is overused)" if row["queue_overused"] else ""
+    if fits:
+        rel = count[_abi.TWHY_FITS_RELEASING]
+        return f"{fits}/{total} nodes are available" + (f", {rel} of them once resources are released" if rel else "") \
+            + f".{tail}"
+    parts = sorted(f"{n} {text}" for n, text in zip(count, STAGE_TEXTS) if n > 0)
+    if count[_abi.TWHY_PANIC]:
+        parts.append(f"{count[_abi.TWHY_PANIC]} have no Node object")
+    parts += sorted(f"{v} insufficient {k}" for k, v in zip(("cpu", "memory", "GPU"), row["idle_short"]) if v > 0)
+    if not parts:
+        return f"0/{total} nodes are available.{tail}"
+    return f"0/{total} nodes are available: {', '.join(parts)}.{tail}"
+
+
 def reasons_row(st):
     """A kbg_job_reasons as the output rows carry it."""
     return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),

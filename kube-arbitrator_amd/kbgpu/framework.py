@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _abi
-from .api import ALLOCATED, BINDING, PIPELINED, RELEASING, pod_key
+from .api import ALLOCATED, BINDING, PENDING, PIPELINED, RELEASING, pod_key
 from .snapshot import FlatSnapshot
 
 KNOWN_PLUGINS = ("priority", "gang", "drf", "predicates", "proportion")
@@ -592,6 +592,21 @@ class Session:
         out = (_abi.kbg_victim_why * max(n, 1))()
         _abi.check(_abi.lib().kbg_victim_reasons(self.handle, int(mode), arr, n, out))
         return list(out[:n])
+
+    def task_reasons(self, tasks=None):
+        """One dict per task (the indices `tasks`, or every task Pending now in
+        the mirror): why it would not be placed now, every live node under one
+        cause against the session as it is (kbg_task_why). Legal any time
+        after open on sessions opened with reasons=True; changes nothing."""
+        if tasks is None:
+            tasks = [t for t, obj in enumerate(self.flat.task_objs) if obj is not None and obj.status == PENDING]
+        n = len(tasks)
+        arr = (ctypes.c_int32 * max(n, 1))(*tasks)
+        out = (_abi.kbg_task_why * max(n, 1))()
+        _abi.check(_abi.lib().kbg_task_reasons(self.handle, arr, n, out))
+        return [{"valid": bool(r.valid), "task": r.task, "visited": r.visited, "best_effort": bool(r.best_effort),
+                 "queue_overused": bool(r.queue_overused), "count": list(r.count), "first_node": list(r.first_node),
+                 "idle_short": list(r.idle_short)} for r in out[:n]]
 
     def queue_state(self, q):
         st = _abi.kbg_queue_state()

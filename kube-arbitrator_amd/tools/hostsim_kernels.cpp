@@ -9,7 +9,8 @@
 // tests/test_hostsim_kernels.py holds them to the references the GPU kernels
 // are held to (tests/kernel_ref.py, tests/victim_ref.py);
 // tests/test_hostsim_victim_why.py does so for the victim-reasons launchers
-// (tests/victim_why_ref.py).
+// (tests/victim_why_ref.py), tests/test_hostsim_task_why.py for the
+// pending-task reasons (tests/task_why_ref.py).
 //
 // The victim launchers count their launches (kbg_hostsim_launch_counts, an
 // export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
@@ -576,6 +577,54 @@ void victim_why_big_run(const VictimWhyArgs& a, const VictimTables& t, const int
     }
 }
 
+// ---- pending-task reasons (kbg_device.hpp TaskWhy): the cause of table row
+// `row` for shape sh, and the dimensions in which Idle.FitDelta(req) is
+// negative (bits 0..2 of *idle_short, set for causes 7 and 8 only). The node is
+// live and inside the table.
+int32_t task_why_cause(const TaskWhyArgs& a, const Table& t, const TaskShape& sh, int32_t row, int32_t* idle_short) {
+  *idle_short = 0;
+  const int32_t n = a.tab_lo + row;
+  const uint64_t bit = 1ull << (n & 63);
+  if (a.cap_check) {  // predicates.go:125-183, the first failing stage
+    if (t.nt[row] >= t.mt[row]) return 0;
+    if (!(a.sel_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) return 1;
+    if (a.unsched[n >> 6] & bit) return 3;
+    if (!(a.taint_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) return 4;
+  }
+  if (sh.flags & kTaskShapeBestEffort) return kTwhyFitsIdle;  // backfill.go:47-60: no resource test
+  if (fits(false, sh.req, t.ic[row], t.im[row], t.ig[row])) return kTwhyFitsIdle;
+  const double idle[3] = {t.ic[row], t.im[row], t.ig[row]};
+  const double mn[3] = {kMinMilliCPU, kMinMemory, kMinMilliGPU};
+  for (int d = 0; d < 3; ++d)  // Resource.FitDelta (resource_info.go:116-129)
+    if ((sh.req[d] > 0 ? idle[d] - (sh.req[d] + mn[d]) : idle[d]) < 0) *idle_short |= 1 << d;
+  return fits(false, sh.req, t.rc[row], t.rm[row], t.rg[row]) ? kTwhyFitsReleasing : kTwhyShort;
+}
+
+void task_why_init_run(int32_t* out, int32_t n_shapes) {
+  for (int32_t s = 0; s < n_shapes; ++s) {
+    int32_t* o = out + (size_t)s * kTaskWhyOut;
+    std::fill(o, o + kTaskWhyOut, 0);
+    std::fill(o + kTwhyCauses, o + 2 * kTwhyCauses, -1);
+  }
+}
+
+void task_why_run(const TaskWhyArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  for (int32_t s = 0; s < a.n_shapes; ++s) {
+    int32_t* o = a.out + (size_t)s * kTaskWhyOut;
+    for (int32_t row = 0; row < a.tab_n; ++row) {
+      const int32_t n = a.tab_lo + row;
+      if (!((a.live[n >> 6] >> (n & 63)) & 1ull)) continue;
+      int32_t idle_short = 0;
+      const int32_t c = task_why_cause(a, t, a.shapes[s], row, &idle_short);
+      o[c]++;
+      if (o[kTwhyCauses + c] < 0 || n < o[kTwhyCauses + c]) o[kTwhyCauses + c] = n;
+      for (int d = 0; d < 3; ++d)
+        if ((idle_short >> d) & 1) o[2 * kTwhyCauses + d]++;
+    }
+  }
+}
+
 void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
   n.idle_cpu[d.node] = d.idle[0];
   n.idle_mem[d.node] = d.idle[1];
@@ -611,11 +660,12 @@ enum Count : int {
   kCountPrepInline,
   kCountPrepInlineNodes,
   kCountPrepInlineState,
+  kCountTaskWhy,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -781,6 +831,17 @@ hipError_t launch_victim_why_big(const VictimWhyArgs& a, const VictimTables& t, 
                                  hipStream_t stream) {
   if (n_rows <= 0 || a.nq <= 0) return hipSuccess;
   return launch(stream, nullptr, nullptr, [a, t, rows, n_rows] { victim_why_big_run(a, t, rows, n_rows); });
+}
+
+hipError_t launch_task_why_init(int32_t* out, int32_t n_shapes, hipStream_t stream) {
+  if (n_shapes <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [out, n_shapes] { task_why_init_run(out, n_shapes); });
+}
+
+hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
+  g_count[kCountTaskWhy]++;
+  return launch(stream, start, stop, [a] { task_why_run(a); });
 }
 
 }  // namespace kbg
