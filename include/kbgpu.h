@@ -749,6 +749,46 @@ typedef struct kbg_task_why {
  * communicator or without a device. The call changes nothing: every later
  * action returns what it would have. */
 kbg_status kbg_task_reasons(kbg_session* s, const int32_t* tasks, int32_t n_tasks, kbg_task_why* out);
+
+/* How many copies of a Pending task fit now (additive within KBG_ABI_VERSION
+ * 13): one row per named task. Every live node of ssn.Nodes that passes the
+ * predicates plugin for the task NOW (as kbg_task_reasons evaluates it) takes
+ * copies one after the other as allocate would place identical tasks in a row
+ * (allocate.go:119-162, node_info.go:101-129, resource_info.go:100-110,142-146):
+ *   room  = maxtasks - ntasks under the predicates plugin (predicates.go:125-127)
+ *   bound = min(limit, room)
+ *   a = Idle;      while (i < bound && Resreq.LessEqual(a)) { a.Sub(Resreq); ++i; }  k_idle
+ *   b = Releasing; while (i < bound && Resreq.LessEqual(b)) { b.Sub(Resreq); ++i; }  k_rel
+ * in fp64, one copy at a time. A BestEffort task takes no resource test
+ * (backfill.go:47-60): k_idle = bound. The hypothetical copies have pod keys of
+ * their own (node_info.go:101-106 does not apply to them). A class with a host
+ * port holds one copy per node at most. In a session with pod affinity the
+ * verdict of now is applied to every copy; what the copies would do to each
+ * other's (anti)affinity is not modelled, and affinity_now is 1. */
+typedef struct kbg_task_room {
+  int32_t valid;                /* 0: the task is not Pending now; nothing below is set */
+  int32_t task;
+  int32_t best_effort;          /* Resreq.IsEmpty(): backfill's task, no resource test */
+  int32_t queue_overused;       /* Overused(queue) holds now: allocate would skip the queue (allocate.go:70-74) */
+  int32_t limit;                /* the call's limit */
+  int32_t nodes_pass;           /* live nodes past the predicates */
+  int32_t copies_idle;          /* sum of k_idle: room now */
+  int32_t copies_releasing;     /* sum of k_rel: more on resources being released */
+  int32_t nodes_idle;           /* nodes with k_idle > 0 */
+  int32_t nodes_releasing_only; /* nodes with k_idle == 0 && k_rel > 0 */
+  int32_t first_node;           /* lowest node with k_idle + k_rel > 0, -1 when none */
+  int32_t max_node_copies;      /* max of k_idle + k_rel */
+  int32_t limit_hit;            /* nodes cut at limit below their pod room: the sums are lower bounds */
+  int32_t affinity_now;         /* the session has pod affinity: see above */
+  int32_t panic_nodes;          /* live nodes with a nil Node (predicates.go:122-123): they contribute nothing */
+  int32_t reserved[1];
+} kbg_task_room;
+/* out[i] describes tasks[i]; limit outside [1, 1024] is KBG_E_INVALID, as is
+ * nodes * limit > INT32_MAX. Everything else as kbg_task_reasons: legal any
+ * time after open on a session opened with kbg_options.reasons,
+ * KBG_E_UNSUPPORTED over a communicator or without a device. The call changes
+ * nothing: every later action returns what it would have. */
+kbg_status kbg_task_headroom(kbg_session* s, const int32_t* tasks, int32_t n_tasks, int32_t limit, kbg_task_room* out);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

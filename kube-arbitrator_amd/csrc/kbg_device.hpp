@@ -471,4 +471,63 @@ hipError_t launch_task_why_init(int32_t* out, int32_t n_shapes, hipStream_t stre
 hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
                            hipEvent_t stop = nullptr);
 
+// How many copies of a Pending task fit now (kbg_task_headroom). For each of
+// n_shapes shapes (TaskShape, as above) and every node n of the table range
+// whose `live` bit is set and which passes the static stages exactly as in
+// launch_task_why (cap_check: ntasks < maxtasks, sel_ok set, unsched clear,
+// taint_ok set; cap_check 0: every live node passes), with `limit` in
+// [1, kRoomMaxLimit] the same for the whole launch:
+//   room  = cap_check ? maxtasks[n] - ntasks[n] : INT32_MAX      (> 0 here)
+//   bound = min(limit, room)
+//   i = 0; a = Idle[n];      while (i < bound && LE(req, a)) { a -= req; ++i; }   k_idle = i
+//          b = Releasing[n]; while (i < bound && LE(req, b)) { b -= req; ++i; }   k_rel  = i - k_idle
+// the copies allocate would put on the node one after the other
+// (allocate.go:119-162: LessEqual(Idle) then Idle.Sub, else LessEqual
+// (Releasing) then Releasing.Sub, node_info.go:101-129), under the pod cap of
+// predicates.go:125-127. LE is the reference's `r < x || |x - r| < min` per
+// dimension and the subtraction plain fp64 per dimension, one copy at a time:
+// the iteration is the definition (a request dimension below its min keeps
+// fitting while Idle drifts negative; a - k * req is not the iterated value).
+// A BestEffort shape takes no resource test (backfill.go:47-60): k_idle =
+// bound, k_rel = 0.
+// Row s of `out` (kRoomOut words), over those nodes:
+//   kRoomCopiesIdle       sum of k_idle
+//   kRoomCopiesRel        sum of k_rel
+//   kRoomNodesIdle        nodes with k_idle > 0
+//   kRoomNodesRelOnly     nodes with k_idle == 0 && k_rel > 0
+//   kRoomFirstNode        lowest global node with k_idle + k_rel > 0, -1 none
+//   kRoomMaxNodeCopies    max of k_idle + k_rel
+//   kRoomNodesPass        the nodes past the stages
+//   kRoomLimitHit         nodes with k_idle + k_rel == limit and limit < room:
+//                         their count may have been cut, the sums are lower bounds
+// launch_task_headroom_init sets every row to its empty value;
+// launch_task_headroom, after it on the same stream, adds the table's nodes
+// with integer atomics. tab_lo is a multiple of 64. The launcher refuses
+// (hipErrorInvalidValue, nothing launched) a limit outside [1, kRoomMaxLimit]
+// and tab_n * limit > INT32_MAX, so no sum can wrap.
+enum TaskRoom : int32_t {
+  kRoomCopiesIdle = 0,
+  kRoomCopiesRel = 1,
+  kRoomNodesIdle = 2,
+  kRoomNodesRelOnly = 3,
+  kRoomFirstNode = 4,
+  kRoomMaxNodeCopies = 5,
+  kRoomNodesPass = 6,
+  kRoomLimitHit = 7,
+  kRoomOut = 8
+};
+constexpr int32_t kRoomMaxLimit = 1024;
+constexpr int kRoomBits = 11;  // k_idle, k_rel <= kRoomMaxLimit = 2^10
+struct TaskRoomArgs {
+  const double* nodes;  // the node table block (FirstFitArgs.nodes)
+  int32_t stride, W, tab_lo, tab_n;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const TaskShape* shapes;                             // [n_shapes] staged in device memory
+  int32_t n_shapes, cap_check, limit;
+  int32_t* out;  // [n_shapes][kRoomOut]
+};
+hipError_t launch_task_headroom_init(int32_t* out, int32_t n_shapes, hipStream_t stream);
+hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
+                                hipEvent_t stop = nullptr);
+
 }  // namespace kbg

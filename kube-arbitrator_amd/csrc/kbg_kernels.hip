@@ -1593,6 +1593,160 @@ hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t 
   return hipGetLastError();
 }
 
+// ------------------------------------------------- pending-task headroom
+// kbg_task_headroom: how many copies of a shape each node would take one after
+// the other (kbg_device.hpp TaskRoom). kbg_task_why_kernel's geometry: a wave
+// owns one 64-node word and keeps its node records in registers, a lane per
+// node; the workgroup's kTaskWhyWaves waves take consecutive words and its
+// kTaskWhyGroup shapes sit in LDS, read as same-address broadcasts. Per shape
+// the stage mask is built on the scalar unit from the class's stage words and
+// the pod-cap ballot; a lane outside it gets bound 0 and never enters a loop.
+// The two loops run per lane: the reference's LessEqual and a plain fp64
+// subtraction per copy, never a product (the iterated value is the contract).
+// The exec mask narrows as lanes finish and the wave leaves a loop when none is
+// left. The reductions are exact and independent of order: the sums are taken
+// over bit planes (kRoomBits ballots and popcounts), the counts are popcounts
+// of ballots, first_node the lowest bit of a ballot and the max a descent over
+// the bit planes of k_idle + k_rel. Lanes 0..7 put the wave's eight words into
+// the workgroup's LDS row of the shape; after the barrier one atomic per
+// non-empty slot goes to the shape's global row (integer add, unsigned min
+// with the empty value -1 the largest, max), so arrival order is nothing.
+__global__ __launch_bounds__(256) void kbg_task_headroom_init_kernel(int32_t* __restrict__ out, int32_t n_shapes) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_shapes * kRoomOut) return;
+  out[i] = i % kRoomOut == kRoomFirstNode ? -1 : 0;
+}
+
+__global__ __launch_bounds__(64 * kTaskWhyWaves) void kbg_task_headroom_kernel(TaskRoomArgs a) {
+  __shared__ TaskShape s_shape[kTaskWhyGroup];
+  __shared__ uint32_t s_out[kTaskWhyGroup * kRoomOut];
+  constexpr int kShapeWords = sizeof(TaskShape) / 4;
+  const int lane = threadIdx.x & 63;
+  const int s0 = blockIdx.y * kTaskWhyGroup;
+  const int ns = min(kTaskWhyGroup, a.n_shapes - s0);
+  if ((int)threadIdx.x < ns * kShapeWords)
+    reinterpret_cast<uint32_t*>(s_shape)[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.shapes + s0)[threadIdx.x];
+  if ((int)threadIdx.x < kTaskWhyGroup * kRoomOut)
+    s_out[threadIdx.x] = (int)threadIdx.x % kRoomOut == kRoomFirstNode ? 0xffffffffu : 0u;
+  __syncthreads();
+  const int wl = blockIdx.x * kTaskWhyWaves + (int)(threadIdx.x >> 6);  // the wave's word of the table
+  if (wl < ((a.tab_n + 63) >> 6)) {                                     // (wave-uniform)
+    const int w = (a.tab_lo >> 6) + wl;                                 // the global word
+    const int r = min(wl * 64 + lane, a.tab_n - 1);                     // a legal row for the ragged word's lanes
+    const size_t L = (size_t)a.stride;
+    const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * L);
+    const double ic = a.nodes[r], im = a.nodes[L + r], ig = a.nodes[2 * L + r];
+    const double rc = a.nodes[3 * L + r], rm = a.nodes[4 * L + r], rg = a.nodes[5 * L + r];
+    const int32_t nt = ni[r], mt = ni[L + r];
+    uint64_t valid = a.live[w];
+    if (wl * 64 + 64 > a.tab_n) valid &= (1ull << (a.tab_n - wl * 64)) - 1ull;  // bits past the table's last node
+    const uint64_t capped = a.cap_check ? __ballot(nt >= mt) : 0ull;             // predicates.go:125-127
+    const uint64_t uns = a.cap_check ? a.unsched[w] : 0ull;
+    const uint64_t open = valid & ~capped & ~uns;
+    // room > 0 on every lane the stage mask keeps (a capped lane's value is never used)
+    const int32_t room = a.cap_check ? (int32_t)((uint32_t)mt - (uint32_t)nt) : INT32_MAX;
+    const int32_t lim = min(a.limit, room);
+    for (int s = 0; s < ns; ++s) {
+      const TaskShape& sh = s_shape[s];
+      const uint64_t so = a.cap_check ? a.sel_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+      const uint64_t to = a.cap_check ? a.taint_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+      const uint64_t pass = open & so & to;  // predicates.go:129-183
+      if (!pass) continue;                   // (wave-uniform)
+      const double q0 = sh.req[0], q1 = sh.req[1], q2 = sh.req[2];
+      const int32_t bound = (pass >> lane) & 1ull ? lim : 0;
+      int32_t ki, kt;
+      if (sh.flags & kTaskShapeBestEffort) {  // backfill.go:47-60: no resource test
+        ki = kt = bound;
+      } else {
+        int32_t i = 0;
+        double x0 = ic, x1 = im, x2 = ig;
+        while (i < bound && le(q0, x0, kMinMilliCPU) && le(q1, x1, kMinMemory) && le(q2, x2, kMinMilliGPU)) {
+          x0 -= q0;  // Resource.Sub (resource_info.go:100-110)
+          x1 -= q1;
+          x2 -= q2;
+          ++i;
+        }
+        ki = i;
+        x0 = rc, x1 = rm, x2 = rg;
+        while (i < bound && le(q0, x0, kMinMilliCPU) && le(q1, x1, kMinMemory) && le(q2, x2, kMinMilliGPU)) {
+          x0 -= q0;
+          x1 -= q1;
+          x2 -= q2;
+          ++i;
+        }
+        kt = i;
+      }
+      const int32_t kr = kt - ki;
+      const uint64_t any = __ballot(kt > 0);
+      uint32_t sum_i = 0, sum_r = 0, mx = 0;
+      if (any) {  // (wave-uniform)
+        uint64_t top = any;  // the lanes still holding the max's leading bits
+        for (int b = kRoomBits - 1; b >= 0; --b) {
+          sum_i += (uint32_t)__popcll(__ballot((ki >> b) & 1)) << b;
+          sum_r += (uint32_t)__popcll(__ballot((kr >> b) & 1)) << b;
+          const uint64_t tb = top & __ballot((kt >> b) & 1);
+          if (tb) {
+            top = tb;
+            mx |= 1u << b;
+          }
+        }
+      }
+      const uint64_t m_idle = __ballot(ki > 0);
+      const uint64_t m_hit = __ballot(bound > 0 && kt == a.limit && a.limit < room);
+      const uint32_t v = lane == kRoomCopiesIdle      ? sum_i
+                         : lane == kRoomCopiesRel     ? sum_r
+                         : lane == kRoomNodesIdle     ? (uint32_t)__popcll(m_idle)
+                         : lane == kRoomNodesRelOnly  ? (uint32_t)__popcll(any & ~m_idle)
+                         : lane == kRoomFirstNode     ? (any ? (uint32_t)(w * 64 + __builtin_ctzll(any)) : 0xffffffffu)
+                         : lane == kRoomMaxNodeCopies ? mx
+                         : lane == kRoomNodesPass     ? (uint32_t)__popcll(pass)
+                         : lane == kRoomLimitHit      ? (uint32_t)__popcll(m_hit)
+                                                      : 0u;
+      if (lane < kRoomOut) {
+        uint32_t* o = s_out + s * kRoomOut + lane;
+        if (lane == kRoomFirstNode)
+          atomicMin(o, v);
+        else if (lane == kRoomMaxNodeCopies)
+          atomicMax(o, v);
+        else if (v)
+          atomicAdd(o, v);
+      }
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < ns * kRoomOut) {
+    const int k = (int)threadIdx.x % kRoomOut;
+    const uint32_t v = s_out[threadIdx.x];
+    uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + (size_t)s0 * kRoomOut + threadIdx.x;
+    if (k == kRoomFirstNode) {
+      if (v != 0xffffffffu) atomicMin(o, v);
+    } else if (v) {
+      if (k == kRoomMaxNodeCopies)
+        atomicMax(o, v);
+      else
+        atomicAdd(o, v);
+    }
+  }
+}
+
+hipError_t launch_task_headroom_init(int32_t* out, int32_t n_shapes, hipStream_t stream) {
+  if (n_shapes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kbg_task_headroom_init_kernel, dim3((n_shapes * kRoomOut + 255) / 256), dim3(256), 0, stream, out,
+                     n_shapes);
+  return hipGetLastError();
+}
+
+hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.limit < 1 || a.limit > kRoomMaxLimit) return hipErrorInvalidValue;
+  if ((int64_t)a.tab_n * a.limit > INT32_MAX) return hipErrorInvalidValue;  // a sum could wrap
+  if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
+  const int words = (a.tab_n + 63) >> 6;
+  hipExtLaunchKernelGGL(kbg_task_headroom_kernel,
+                        dim3((words + kTaskWhyWaves - 1) / kTaskWhyWaves, (a.n_shapes + kTaskWhyGroup - 1) / kTaskWhyGroup),
+                        dim3(64 * kTaskWhyWaves), 0, stream, start, stop, 0, a);
+  return hipGetLastError();
+}
+
 __device__ __forceinline__ void apply_node_delta(const NodeSoA& nd, const NodeDelta& x) {
   nd.idle_cpu[x.node] = x.idle[0];
   nd.idle_mem[x.node] = x.idle[1];

@@ -776,6 +776,9 @@ void free_device(Session& S) {
   S.d_twhy_shapes = nullptr;  // (d_allocs too)
   S.d_twhy_out = nullptr;
   S.twhy_cap = 0;
+  S.d_room_shapes = nullptr;  // (d_allocs too)
+  S.d_room_out = nullptr;
+  S.room_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1093,6 +1096,8 @@ kbg_status device_scan(Session& S, kbg::Stage& sg, int32_t G, int32_t base) {
 #include "kbg_victims.ipp"  // preempt / reclaim and their victim scans
 
 #include "kbg_task_why.ipp"  // kbg_task_reasons: why a Pending task would not be placed now
+
+#include "kbg_headroom.ipp"  // kbg_task_headroom: how many copies of a Pending task fit now
 
 #include "kbg_update.ipp"  // resident session updates (kbg_session_update)
 
@@ -1447,6 +1452,18 @@ kbg_status kbg_task_reasons(kbg_session* s, const int32_t* tasks, int32_t n_task
   if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
   try {
     return task_reasons(s->s, tasks, n_tasks, out);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
+}
+
+kbg_status kbg_task_headroom(kbg_session* s, const int32_t* tasks, int32_t n_tasks, int32_t limit, kbg_task_room* out) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return task_headroom(s->s, tasks, n_tasks, limit, out);
   } catch (const std::bad_alloc&) {
     return fail(KBG_E_NOMEM, "host allocation failed");
   } catch (const std::exception& e) {

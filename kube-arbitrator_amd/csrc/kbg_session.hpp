@@ -583,6 +583,10 @@ struct Session {
   kbg::TaskShape* d_twhy_shapes = nullptr;
   int32_t* d_twhy_out = nullptr;
   size_t twhy_cap = 0;                                // shapes both hold
+  // kbg_task_headroom: the staged shapes and their result rows (HBM, grown on demand)
+  kbg::TaskShape* d_room_shapes = nullptr;
+  int32_t* d_room_out = nullptr;
+  size_t room_cap = 0;                                // shapes both hold
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while

@@ -186,6 +186,17 @@ class kbg_task_why(ctypes.Structure):
                 ("count", i32 * 10), ("first_node", i32 * 10), ("idle_short", i32 * 3), ("reserved", i32 * 3)]
 
 
+# kbg_task_headroom: the largest limit a call may name (kRoomMaxLimit)
+ROOM_MAX_LIMIT = 1024
+
+
+class kbg_task_room(ctypes.Structure):
+    _fields_ = [("valid", i32), ("task", i32), ("best_effort", i32), ("queue_overused", i32), ("limit", i32),
+                ("nodes_pass", i32), ("copies_idle", i32), ("copies_releasing", i32), ("nodes_idle", i32),
+                ("nodes_releasing_only", i32), ("first_node", i32), ("max_node_copies", i32), ("limit_hit", i32),
+                ("affinity_now", i32), ("panic_nodes", i32), ("reserved", i32 * 1)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -278,6 +289,7 @@ SIGNATURES = {
     "kbg_job_reasons_get": (i32, [ctypes.c_void_p, i32, P(kbg_job_reasons)]),
     "kbg_victim_reasons": (i32, [ctypes.c_void_p, i32, P(i32), i32, P(kbg_victim_why)]),
     "kbg_task_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_task_why)]),
+    "kbg_task_headroom": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_task_room)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

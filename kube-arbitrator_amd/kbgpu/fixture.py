@@ -103,6 +103,21 @@ def pending_message(row):
     return f"0/{total} nodes are available: {', '.join(parts)}.{tail}"
 
 
+def headroom_message(row, needed):
+    """One line for a job that still needs `needed` members (a Session.
+    task_headroom row of one of its Pending tasks): how many of them have room
+    now, how many more on resources that are being released, on how many
+    nodes; "lower bound" where the call's limit cut a node's count."""
+    if not row["valid"]:
+        return "not pending"
+    nodes = row["nodes_idle"] + row["nodes_releasing_only"]
+    tail = ", lower bound" if row["limit_hit"] else ""
+    tail += " (pod affinity as it is now)" if row["affinity_now"] else ""
+    tail += " (its queue is overused)" if row["queue_overused"] else ""
+    return (f"needs {needed} more; room for {row['copies_idle']} now, {row['copies_releasing']} more on releasing "
+            f"resources ({nodes} nodes){tail}")
+
+
 def reasons_row(st):
     """A kbg_job_reasons as the output rows carry it."""
     return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),

@@ -608,6 +608,25 @@ class Session:
                  "queue_overused": bool(r.queue_overused), "count": list(r.count), "first_node": list(r.first_node),
                  "idle_short": list(r.idle_short)} for r in out[:n]]
 
+    def task_headroom(self, tasks=None, limit=_abi.ROOM_MAX_LIMIT):
+        """One dict per task (the indices `tasks`, or every task Pending now in
+        the mirror): how many copies of it fit now, each live node taking up
+        to `limit` (1..1024) copies one after the other from Idle, then from
+        Releasing, under its pod cap (kbg_task_room). Legal any time after
+        open on sessions opened with reasons=True; changes nothing."""
+        if tasks is None:
+            tasks = [t for t, obj in enumerate(self.flat.task_objs) if obj is not None and obj.status == PENDING]
+        n = len(tasks)
+        arr = (ctypes.c_int32 * max(n, 1))(*tasks)
+        out = (_abi.kbg_task_room * max(n, 1))()
+        _abi.check(_abi.lib().kbg_task_headroom(self.handle, arr, n, int(limit), out))
+        return [{"valid": bool(r.valid), "task": r.task, "best_effort": bool(r.best_effort),
+                 "queue_overused": bool(r.queue_overused), "limit": r.limit, "nodes_pass": r.nodes_pass,
+                 "copies_idle": r.copies_idle, "copies_releasing": r.copies_releasing, "nodes_idle": r.nodes_idle,
+                 "nodes_releasing_only": r.nodes_releasing_only, "first_node": r.first_node,
+                 "max_node_copies": r.max_node_copies, "limit_hit": r.limit_hit, "affinity_now": bool(r.affinity_now),
+                 "panic_nodes": r.panic_nodes} for r in out[:n]]
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))

@@ -10,7 +10,8 @@
 // are held to (tests/kernel_ref.py, tests/victim_ref.py);
 // tests/test_hostsim_victim_why.py does so for the victim-reasons launchers
 // (tests/victim_why_ref.py), tests/test_hostsim_task_why.py for the
-// pending-task reasons (tests/task_why_ref.py).
+// pending-task reasons (tests/task_why_ref.py), tests/test_hostsim_headroom.py
+// for the pending-task headroom (tests/headroom_ref.py).
 //
 // The victim launchers count their launches (kbg_hostsim_launch_counts, an
 // export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
@@ -625,6 +626,71 @@ void task_why_run(const TaskWhyArgs& a) {
   }
 }
 
+// ---- pending-task headroom (kbg_device.hpp TaskRoom): the copies of shape sh
+// table row `row` takes one after the other, {from Idle, from Releasing}, with
+// *pass whether the node is past the stages and *cut whether `limit` ended the
+// count below the node's pod room. The node is live and inside the table.
+std::pair<int32_t, int32_t> task_room_node(const TaskRoomArgs& a, const Table& t, const TaskShape& sh, int32_t row,
+                                           bool* pass, bool* cut) {
+  *pass = *cut = false;
+  const int32_t n = a.tab_lo + row;
+  const uint64_t bit = 1ull << (n & 63);
+  int64_t room = INT32_MAX;
+  if (a.cap_check) {  // predicates.go:125-183
+    if (t.nt[row] >= t.mt[row]) return {0, 0};
+    if (!(a.sel_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) return {0, 0};
+    if (a.unsched[n >> 6] & bit) return {0, 0};
+    if (!(a.taint_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) return {0, 0};
+    room = (int64_t)t.mt[row] - t.nt[row];
+  }
+  *pass = true;
+  const int32_t bound = (int32_t)std::min<int64_t>(a.limit, room);
+  int32_t i = 0, k_idle;
+  if (sh.flags & kTaskShapeBestEffort) {  // backfill.go:47-60: no resource test
+    i = k_idle = bound;
+  } else {
+    double x[3] = {t.ic[row], t.im[row], t.ig[row]};
+    for (; i < bound && fits(false, sh.req, x[0], x[1], x[2]); ++i)  // Idle.Sub (node_info.go:108-118)
+      for (int d = 0; d < 3; ++d) x[d] -= sh.req[d];
+    k_idle = i;
+    double y[3] = {t.rc[row], t.rm[row], t.rg[row]};
+    for (; i < bound && fits(false, sh.req, y[0], y[1], y[2]); ++i)  // Releasing.Sub (node_info.go:119-126)
+      for (int d = 0; d < 3; ++d) y[d] -= sh.req[d];
+  }
+  *cut = i == a.limit && a.limit < room;
+  return {k_idle, i - k_idle};
+}
+
+void task_headroom_init_run(int32_t* out, int32_t n_shapes) {
+  for (int32_t s = 0; s < n_shapes; ++s) {
+    int32_t* o = out + (size_t)s * kRoomOut;
+    std::fill(o, o + kRoomOut, 0);
+    o[kRoomFirstNode] = -1;
+  }
+}
+
+void task_headroom_run(const TaskRoomArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  for (int32_t s = 0; s < a.n_shapes; ++s) {
+    int32_t* o = a.out + (size_t)s * kRoomOut;
+    for (int32_t row = 0; row < a.tab_n; ++row) {
+      const int32_t n = a.tab_lo + row;
+      if (!((a.live[n >> 6] >> (n & 63)) & 1ull)) continue;
+      bool pass, cut;
+      const auto [k_idle, k_rel] = task_room_node(a, t, a.shapes[s], row, &pass, &cut);
+      if (!pass) continue;
+      o[kRoomNodesPass]++;
+      o[kRoomCopiesIdle] += k_idle;
+      o[kRoomCopiesRel] += k_rel;
+      if (k_idle > 0) o[kRoomNodesIdle]++;
+      if (k_idle == 0 && k_rel > 0) o[kRoomNodesRelOnly]++;
+      if (k_idle + k_rel > 0 && (o[kRoomFirstNode] < 0 || n < o[kRoomFirstNode])) o[kRoomFirstNode] = n;
+      o[kRoomMaxNodeCopies] = std::max(o[kRoomMaxNodeCopies], k_idle + k_rel);
+      if (cut) o[kRoomLimitHit]++;
+    }
+  }
+}
+
 void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
   n.idle_cpu[d.node] = d.idle[0];
   n.idle_mem[d.node] = d.idle[1];
@@ -661,11 +727,12 @@ enum Count : int {
   kCountPrepInlineNodes,
   kCountPrepInlineState,
   kCountTaskWhy,
+  kCountTaskHeadroom,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state,task_why";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -842,6 +909,19 @@ hipError_t launch_task_why(const TaskWhyArgs& a, hipStream_t stream, hipEvent_t 
   if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
   g_count[kCountTaskWhy]++;
   return launch(stream, start, stop, [a] { task_why_run(a); });
+}
+
+hipError_t launch_task_headroom_init(int32_t* out, int32_t n_shapes, hipStream_t stream) {
+  if (n_shapes <= 0) return hipSuccess;
+  return launch(stream, nullptr, nullptr, [out, n_shapes] { task_headroom_init_run(out, n_shapes); });
+}
+
+hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (a.limit < 1 || a.limit > kRoomMaxLimit) return hipErrorInvalidValue;
+  if ((int64_t)a.tab_n * a.limit > INT32_MAX) return hipErrorInvalidValue;
+  if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
+  g_count[kCountTaskHeadroom]++;
+  return launch(stream, start, stop, [a] { task_headroom_run(a); });
 }
 
 }  // namespace kbg

@@ -7,7 +7,9 @@
 // tests/test_victim_kernels_gpu.py does so for the victim scan
 // (tests/victim_ref.py), tests/test_victim_why_kernels_gpu.py for the victim
 // reasons (tests/victim_why_ref.py), tests/test_task_why_kernels_gpu.py for
-// the pending-task reasons (tests/task_why_ref.py).
+// the pending-task reasons (tests/task_why_ref.py),
+// tests/test_headroom_kernels_gpu.py for the pending-task headroom
+// (tests/headroom_ref.py).
 //
 // Output buffers are filled with kProbeSentinel bytes before the launch and
 // are followed by a guard region of kProbeGuardBytes of the same pattern; the
@@ -843,6 +845,70 @@ extern "C" int32_t kbg_tool_probe_task_why(const kbg_probe_task_why* p, void* no
 
   PROBE_TRY(kbg::launch_task_why_init(a.out, a.n_shapes, sc.stream));
   PROBE_TRY(kbg::launch_task_why(a, sc.stream));
+  PROBE_TRY(hipStreamSynchronize(sc.stream));
+  PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// kbg_task_headroom_init_kernel, then kbg_task_headroom_kernel, as
+// kbg_task_headroom runs them for n_shapes shapes at once.
+struct kbg_probe_task_headroom {
+  int32_t n_nodes, W, tab_lo, tab_n;  // the table holds the global nodes [tab_lo, tab_lo + tab_n)
+  int32_t stride;                     // rows of the node table block (row = node - tab_lo)
+  int32_t classes;                    // rows of the per-class stage planes
+  int32_t n_shapes, cap_check;
+  int32_t limit;  // copies counted per node at most, 1..kRoomMaxLimit
+};
+
+// The arrays of kbg_tool_probe_task_why. out: n_shapes * kRoomOut words +
+// guard, device memory filled with the sentinel before the launches. A limit
+// outside [1, kRoomMaxLimit] and tab_n * limit > INT32_MAX are refused here as
+// launch_task_headroom refuses them. The node block is copied back so the
+// caller sees it untouched.
+extern "C" int32_t kbg_tool_probe_task_headroom(const kbg_probe_task_headroom* p, void* nodes, const uint64_t* planes,
+                                                const kbg::TaskShape* shapes, void* out) {
+  t_error.clear();
+  if (!p || !nodes || !shapes || !out) return reject("null argument");
+  if (!planes) return reject("null planes");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->tab_lo < 0 || (p->tab_lo & 63)) return reject("tab_lo not a multiple of 64");
+  if (p->tab_n < 1 || (int64_t)p->tab_lo + p->tab_n > p->n_nodes) return reject("node range outside n_nodes");
+  if (p->stride < 1 || p->tab_n > p->stride) return reject("node range outside the table block");
+  if (p->classes < 1) return reject("no class");
+  if (p->n_shapes < 1 || p->n_shapes > (1 << 20)) return reject("n_shapes outside 1..2^20");
+  if (p->limit < 1 || p->limit > kbg::kRoomMaxLimit) return reject("limit outside 1..1024");
+  if ((int64_t)p->tab_n * p->limit > INT32_MAX) return reject("tab_n * limit overflows a row's sums");
+  for (int32_t i = 0; i < p->n_shapes; ++i)
+    if (shapes[i].cls < 0 || shapes[i].cls >= p->classes) return reject("shape: cls outside the planes");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)p->stride;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  uint64_t* d_planes = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_planes, planes, kbg::kbg_stage_words(p->classes, p->W)));
+  const kbg::StagePlanes sp = kbg::kbg_stage_planes(d_planes, p->classes, p->W);
+  kbg::TaskRoomArgs a{};
+  a.nodes = d;
+  a.stride = p->stride;
+  a.W = p->W;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  a.sel_ok = sp.sel_ok;
+  a.taint_ok = sp.taint_ok;
+  a.unsched = sp.unsched;
+  a.live = sp.live;
+  PROBE_TRY(dev_copy(sc, (kbg::TaskShape**)&a.shapes, shapes, (size_t)p->n_shapes));
+  a.n_shapes = p->n_shapes;
+  a.cap_check = p->cap_check ? 1 : 0;
+  a.limit = p->limit;
+  const size_t out_bytes = (size_t)p->n_shapes * kbg::kRoomOut * 4 + kProbeGuardBytes;
+  PROBE_TRY(dev_copy(sc, (char**)&a.out, (const char*)nullptr, out_bytes, kProbeSentinel));
+
+  PROBE_TRY(kbg::launch_task_headroom_init(a.out, a.n_shapes, sc.stream));
+  PROBE_TRY(kbg::launch_task_headroom(a, sc.stream));
   PROBE_TRY(hipStreamSynchronize(sc.stream));
   PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
