@@ -728,11 +728,13 @@ enum Count : int {
   kCountPrepInlineState,
   kCountTaskWhy,
   kCountTaskHeadroom,
+  kCountStageMask,
+  kCountVictimWhy,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,victim_why";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -841,6 +843,7 @@ hipError_t launch_build_class_mask(const StaticTables& t, int32_t n_classes, int
 hipError_t launch_build_stage_planes(const StaticTables& t, int32_t n_classes, int32_t W, const StagePlanes& p,
                                      hipStream_t stream) {
   if (n_classes <= 0 || W <= 0) return hipSuccess;
+  g_count[kCountStageMask]++;
   return launch(stream, nullptr, nullptr, [t, n_classes, W, p] { stage_planes_run(t, n_classes, W, p); });
 }
 
@@ -887,10 +890,11 @@ hipError_t launch_victim_prep_inline(const NodeSoA& n, const VictimTables& t, co
   });
 }
 
-// (not counted: the launch counters describe the actions' own launches)
+// (under a counter of its own: the victim counters describe the actions' own launches)
 hipError_t launch_victim_why(const VictimWhyArgs& a, const VictimTables& t, hipStream_t stream, hipEvent_t start,
                              hipEvent_t stop) {
   if (a.nq <= 0) return hipSuccess;
+  g_count[kCountVictimWhy]++;
   return launch(stream, start, stop, [a, t] { victim_why_run(a, t); });
 }
 

@@ -23,6 +23,11 @@ whatever the session holds:
   nodes_pass == count[6] + count[7] + count[8], first_node the lower of the
   two causes' first nodes, panic_nodes == count[PANIC].
 
+`check_resident` takes one session through helpers.churn_chain
+(kbg_session_reset, kbg_session_update between the cycles) and holds its rows,
+before and after each round's actions and at two limits, to a fresh session's
+on the round's fixture and to `expected_rows` on that fixture.
+
 `check_allocate` is independent of all that: on small hand-built clusters
 whose only Pending pods are M identical copies, the ORACLE's allocate itself
 places copies until none fits; its Allocate and Pipeline decisions, counted
@@ -234,6 +239,71 @@ def check_refusals(fx):
     finally:
         ssn.close()
     return errs
+
+
+def check_resident(fx0, seed, rounds, opts=None, limits=(2, _abi.ROOM_MAX_LIMIT)):
+    """A resident session (kbg_session_reset, kbg_session_update) over
+    helpers.churn_chain: before the round's first action and after its
+    actions, at both limits, its rows against a fresh session's on the round's
+    fixture (task by uid, node by name) and against `expected_rows` on that
+    fixture, the fresh mirror at open and the oracle's output of the round.
+    Returns (errors, rows compared)."""
+    import ctypes
+    errs, said = [], 0
+    ssn = None
+    L = _abi.lib()
+    aff = ts.has_pod_affinity(fx0)
+
+    def named(s, rows):
+        names = s.flat.node_names
+        return sorted([s.flat.task_objs[r["task"]].uid] +
+                      [names[v] if k == "first_node" and v >= 0 else v for k, v in sorted(r.items()) if k != "task"]
+                      for r in rows)
+
+    try:
+        for r, (fx, changes, ref_full) in enumerate(ws.resident_rounds(fx0, seed, rounds)):
+            assert ref_full["status"] == "ok", ref_full.get("error")
+            actions = fx.get("actions") or ["allocate"]
+            if ssn is None:
+                ssn, _ = ws.open_with_reasons(fx, opts)
+            else:
+                _abi.check(L.kbg_session_reset(ssn.handle))
+                ssn.update(changes)
+            fresh, _ = ws.open_with_reasons(fx, opts)
+            try:
+                snap = ts.OpenSnap(fresh)
+                rules = ws.plugin_rules(fresh.tiers)
+                if list(ssn.flat.node_names) != list(fresh.flat.node_names):
+                    errs.append(f"round {r}: the resident session's nodes are not in the fresh session's order")
+                    break
+                uid_task = {t.uid: i for i, t in enumerate(ssn.flat.task_objs) if t is not None}
+                refs_ok = not ((aff or ts.has_host_ports(fx)) and not ws.discard_free(snap.mirror, ref_full))
+                for when in ("before", "after"):
+                    if when == "after":
+                        cap = max(1, len(ssn.flat.task_objs))
+                        buf, n = (_abi.kbg_decision * cap)(), ctypes.c_int32(0)
+                        for name in actions:
+                            _abi.check(getattr(L, ws.ENTRY[name])(ssn.handle, buf, cap, ctypes.byref(n)))
+                        ts.run_actions(fresh, actions)
+                    for limit in limits:
+                        tag = f"round {r}, {when} the actions, limit {limit}"
+                        want = fresh.task_headroom(limit=limit)
+                        mine = [uid_task[fresh.flat.task_objs[w["task"]].uid] for w in want]
+                        got = ssn.task_headroom(mine, limit)
+                        if named(fresh, want) != named(ssn, got):
+                            errs.append(f"{tag}: the resident session's rows differ from a fresh session's")
+                        said += len(want)
+                        if refs_ok:  # in the fresh session's task numbering, which expected_rows speaks
+                            exp = expected_rows(snap, fx, snap.state if when == "before" else ref_full, rules, limit)
+                            errs += compare_rows(exp, [dict(g, task=w["task"]) for g, w in zip(got, want)], aff, tag)
+            finally:
+                fresh.close()
+    finally:
+        if ssn is not None:
+            ssn.close()
+    if not said:
+        errs.append("no round held a Pending task: the case says nothing")
+    return errs, said
 
 
 def check_kat(fx):

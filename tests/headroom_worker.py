@@ -29,7 +29,7 @@ SEEDS = {"random": (1, 5, 7, 8), "contended": (6, 7, 19, 21), "ports": (0, 1, 13
          "affinity": (500, 503, 506, 509)}
 KATS = ("kat_task_why", "kat_reclaim", "kat_preempt")
 ALLOCATE = ("hand", "seed17", "seed70")
-SESSION_CASES = (["kat_headroom-hand", "kat_headroom_dev-hand", "refusals"] + [f"allocate-{a}" for a in ALLOCATE] +
+SESSION_CASES = (["kat_headroom-hand", "kat_headroom_dev-hand", "refusals", "resident"] + [f"allocate-{a}" for a in ALLOCATE] +
                  list(KATS) + [f"{kind}{s}" for kind, seeds in SEEDS.items() for s in seeds])
 
 
@@ -55,6 +55,12 @@ def run_session_case(case, opts=None):
         return hs.check_kat(session_fixture(case[:-5])), None, False
     if case == "refusals":
         return hs.check_refusals(session_fixture("kat_task_why")), None, False
+    if case == "resident":  # the chain of tests/task_why_worker.py's resident case
+        from kbgpu import synth
+        fx = dict(synth.contended_fixture(7), actions=["reclaim", "allocate", "backfill", "preempt"])
+        errs, said = hs.check_resident(fx, seed=7, rounds=2, opts=opts)
+        print(f"resident: {said} rows compared with the fresh session's and the reference's")
+        return errs + ([] if said else ["no row compared"]), None, False
     return hs.check_fixture(session_fixture(case), opts)
 
 

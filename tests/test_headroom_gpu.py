@@ -2,7 +2,8 @@
 tests/headroom_session.py (expected rows from the fixture and the oracle's
 output, the invariants against kbg_task_reasons, the two paths, the logs),
 the hand-derived KATs, the clusters on which the oracle's own allocate places
-identical copies until none fits, and the refusals."""
+identical copies until none fits, a resident session over a churn chain (reset and
+update between cycles) against a fresh session and the reference, and the refusals."""
 import pytest
 
 import headroom_session as hs
@@ -39,6 +40,13 @@ def test_hand_derived_kat(name):
 @pytest.mark.parametrize("name", hw.ALLOCATE)
 def test_row_is_what_the_oracle_s_allocate_places(name):
     errs = hs.check_allocate(hs.allocate_fixtures()[name])
+    assert not errs, "\n".join(errs[:20])
+
+
+def test_resident_session():
+    """Reset and update between cycles: the rows before and after each round's actions, at two limits, against a
+    fresh session's and against the reference on the round's fixture and the oracle's output."""
+    errs, _, _ = hw.run_session_case("resident", OPTS)
     assert not errs, "\n".join(errs[:20])
 
 

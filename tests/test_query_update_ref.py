@@ -1,0 +1,285 @@
+"""The cases of tests/query_update_cases.py say something, and the comparator
+of tests/query_update_ref.py would notice a stale session: both shown from the
+references alone (fixtures, the oracle's output, the reference rows of S0 and
+S1). No kbg library is loaded here.
+
+Per case: Pending tasks before the first action after the update and after
+the last one, and reference rows of S1 that differ from those of the session
+before the update at the same point of the cycle, or the update is invisible
+to the four calls.
+
+Per family, over its cases, the claims its events can carry (CLAIMS): a node
+that moved and is some row's first node, a deleted node that was one, a task
+whose index moved, queue_overused flipping, the victims the gang plugin
+protects changing with MinAvailable, a node moving between two predicate
+stages, copies_idle changing under the same nodes_pass.
+
+The comparator is handed six stand-ins for what a stale session would answer
+(STALE); each must be noticed on at least one case."""
+import copy
+from types import SimpleNamespace
+
+import pytest
+
+import query_update_cases as qc
+import query_update_ref as qr
+import reasons_ref as rr
+import task_why_session as ts
+from update_events import fixture_after, replay
+
+CASES = qc.all_cases()
+# The seven claims, per family, less those its events cannot carry:
+#   structural: node, PodGroup and queue adds and deletes set no MinAvailable of a job that stays
+#     (gang_protection_changes) and update no node (stage_moves);
+#   in_place: JOB_UPDATE / QUEUE_SET and pod churn renumber nothing and touch no node's labels or taints
+#     (moved_first_node, deleted_first_node, task_index_moved, stage_moves);
+#   recompile: node updates alone delete and renumber nothing, and leave queues and MinAvailable as they are
+#     (everything but stage_moves and copies_idle_alone);
+#   chain: all seven.
+CLAIMS = {
+    "structural": ("moved_first_node", "deleted_first_node", "task_index_moved", "queue_overused_flips",
+                   "copies_idle_alone"),
+    "in_place": ("queue_overused_flips", "gang_protection_changes", "copies_idle_alone"),
+    "recompile": ("stage_moves", "copies_idle_alone"),
+    "chain": ("moved_first_node", "deleted_first_node", "task_index_moved", "queue_overused_flips",
+              "gang_protection_changes", "stage_moves", "copies_idle_alone"),
+}
+STALE = ("rows0_unchanged", "first_node_old_numbers", "old_queue_overused", "old_min_available", "other_limit",
+         "wrong_order")
+
+
+def case_references(build):
+    """S0's references and, per round, the batch, the fixture after it and S1's references in the order the
+    session takes (the old order, new names after it: tests/query_update_session.py checks that it does)."""
+    fx0, rounds_of, _ = build()
+    actions = qr.actions_of(fx0)
+    r0 = qr.reference_points(fx0)
+    order, done, rounds = qr.order_of(r0.view), [], []
+    for changes_of in rounds_of:
+        fx_now = fixture_after(fx0, done) if done else fx0
+        ch = changes_of(qr.view_of(replay(fx0, done), order, fx0), fx_now)
+        done.append(ch)
+        fx1 = fixture_after(fx0, done)
+        assert fx1 is not None, "no fixture says the cache after the events"
+        order = qr.order_of(qr.view_of(replay(fx0, done), order, fx0))
+        rounds.append(SimpleNamespace(changes=ch, fx=fx1, refs=qr.reference_points(fx1, order, actions)))
+    return SimpleNamespace(fx0=fx0, r0=r0, rounds=rounds)
+
+
+@pytest.fixture(scope="module")
+def refs():
+    return {case: case_references(build) for case, (_, build) in CASES.items()}
+
+
+def pending_left(r, k):
+    decided = {d["task"] for d in r.points[k]["ref"]["decisions"]}
+    return sum(1 for _, uid, *_ in r.snap.pending if uid not in decided)
+
+
+def rows_of(pt):
+    return {k: pt[k] for k in ("task", "room", "victim") if pt[k] is not None}
+
+
+def steps(c):
+    """(references before, references after) of every round."""
+    prev = c.r0
+    for rnd in c.rounds:
+        yield prev, rnd
+        prev = rnd.refs
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_case_says_something(refs, case):
+    c = refs[case]
+    last = c.rounds[-1].refs
+    assert pending_left(last, 0) > 0 and pending_left(last, len(last.points) - 1) > 0
+    # what a session that missed the update would answer at a point is what the references before it say there
+    for prev, rnd in steps(c):
+        pairs = [(rows_of(p0), rows_of(p1)) for p0, p1 in zip(prev.points, rnd.refs.points)]
+        shared = [(a[k], b[k]) for a, b in pairs for k in a if k in b]
+        assert shared, "the references say no rows of both S0 and S1"
+        assert any(a != b for a, b in shared), "the update is invisible to the calls"
+
+
+# ------------------------------------------------------------------- claims
+def first_nodes(pt):
+    out = set()
+    for r in (pt["task"] or {}).values():
+        out |= {n for n in r["first_node"] if n is not None}
+    for rows in (pt["room"] or {}).values():
+        out |= {r["first_node"] for r in rows.values() if r["first_node"] is not None}
+    for rows in (pt["victim"] or {}).values():
+        for r in rows.values():
+            out |= {n for n in r["first_node"] if n is not None}
+    return out
+
+
+def claim_moved_first_node(a, rnd):
+    n0, n1 = a.view.flat.node_names, rnd.refs.view.flat.node_names
+    moved = {n for n in n1 if n in n0 and n0.index(n) != n1.index(n)}
+    return bool(moved & set().union(*(first_nodes(pt) for pt in rnd.refs.points)))
+
+
+def claim_deleted_first_node(a, rnd):
+    gone = set(a.view.flat.node_names) - set(rnd.refs.view.flat.node_names)
+    return bool(gone & first_nodes(a.points[-1]))
+
+
+def claim_task_index_moved(a, rnd):
+    i0 = {t.uid: i for i, t in enumerate(a.view.flat.task_objs)}
+    i1 = {t.uid: i for i, t in enumerate(rnd.refs.view.flat.task_objs)}
+    with_rows = lambda r: set().union(*((pt["task"] or {}).keys() for pt in r.points))  # noqa: E731
+    return any(i0[u] != i1[u] for u in with_rows(a) & with_rows(rnd.refs))
+
+
+def overused(pt):
+    out = {("task", u): r["queue_overused"] for u, r in (pt["task"] or {}).items()}
+    for mode, rows in (pt["victim"] or {}).items():
+        out.update({("victim", mode, j): r["queue_overused"] for j, r in rows.items()})
+    return out
+
+
+def claim_queue_overused_flips(a, rnd):
+    o0, o1 = overused(a.points[-1]), overused(rnd.refs.points[-1])
+    return any(o0[k] is not None and o1[k] is not None and bool(o0[k]) != bool(o1[k]) for k in o0 if k in o1)
+
+
+def stale_min_victims(a, rnd, k=-1):
+    """S1's victim rows with S0's MinAvailable where the job was there, or None."""
+    r1 = rnd.refs
+    if r1.points[k]["victim"] is None:
+        return None
+    old = dict(zip(a.snap.mirror.job_uids, a.snap.mirror.job_min))
+    mins = [old.get(u, m) for u, m in zip(r1.snap.mirror.job_uids, r1.snap.mirror.job_min)]
+    uid_of = lambda t: r1.view.flat.task_objs[t].uid  # noqa: E731
+    return {mode: qr.victim_rows(r1.snap.mirror, r1.points[k]["ref"], r1.rules, mode, uid_of, r1.view.flat.node_names,
+                                 job_min=mins) for mode in qr.MODES}
+
+
+def claim_gang_protection_changes(a, rnd):
+    if not any(kind.startswith("pod_group") for kind, _ in rnd.changes):
+        return False
+    return any((stale := stale_min_victims(a, rnd, k)) is not None and stale != rnd.refs.points[k]["victim"]
+               for k in range(1, len(rnd.refs.points)))
+
+
+def claim_stage_moves(a, rnd):
+    if not any(kind == "node_update" for kind, _ in rnd.changes):
+        return False
+    old = {n.name: n.node for n in a.view.nodes}
+    for _, _, _, pod, _ in rnd.refs.snap.pending:
+        for n in rnd.refs.view.nodes:
+            if n.name in old and old[n.name] is not None and n.node is not None:
+                s0, s1 = (rr.first_failing_stage(pod, node, 1 << 30, {}) for node in (old[n.name], n.node))
+                if s0 >= 0 and s1 >= 0 and s0 != s1:
+                    return True
+    return False
+
+
+def claim_copies_idle_alone(a, rnd):
+    for k0, k1 in ((-1, -1), (0, 0), (-1, 0)):
+        r0, r1 = a.points[k0]["room"], rnd.refs.points[k1]["room"]
+        if r0 is None or r1 is None:
+            continue
+        for lim in qr.LIMITS:
+            for u in set(r0[lim]) & set(r1[lim]):
+                if r0[lim][u]["copies_idle"] != r1[lim][u]["copies_idle"] and \
+                        r0[lim][u]["nodes_pass"] == r1[lim][u]["nodes_pass"]:
+                    return True
+    return False
+
+
+@pytest.mark.parametrize("family,claim", [(f, c) for f, cs in CLAIMS.items() for c in cs])
+def test_family_carries_the_claim(refs, family, claim):
+    fn = globals()["claim_" + claim]
+    holds = [case for case, (fam, _) in CASES.items() if fam == family
+             and any(fn(a, rnd) for a, rnd in steps(refs[case]))]
+    print(f"{family}: {claim} holds on {holds}")
+    assert holds, f"no {family} case carries {claim}"
+
+
+# ------------------------------------------------------- the comparator sees
+def stale_rows(kind, a, rnd, k):
+    """What a stale session would hand in at point k of S1, or None where the stand-in does not apply."""
+    r1 = rnd.refs
+    pt = r1.points[k]
+    got = copy.deepcopy(qr.point_as_rows(pt))
+    if got["task"] is None:
+        return None
+    if kind == "rows0_unchanged":
+        old = a.points[-1]
+        return None if old["task"] is None else copy.deepcopy(qr.point_as_rows(old))
+    if kind == "first_node_old_numbers":  # the index of S1 read in S0's list of names
+        n0, n1 = a.view.flat.node_names, r1.view.flat.node_names
+        back = lambda n: None if n is None else (n0[n1.index(n)] if n1.index(n) < len(n0) else None)  # noqa: E731
+        for r in got["task"].values():
+            r["first_node"] = [back(n) for n in r["first_node"]]
+        for rows in got["room"].values():
+            for r in rows.values():
+                r["first_node"] = back(r["first_node"])
+        return got
+    if kind == "old_queue_overused":
+        old = overused(a.points[-1])
+        for u, r in got["task"].items():
+            if old.get(("task", u)) is not None:
+                r["queue_overused"] = old[("task", u)]
+        for rows in got["room"].values():
+            for u, r in rows.items():
+                if old.get(("task", u)) is not None:
+                    r["queue_overused"] = old[("task", u)]
+        return got
+    if kind == "old_min_available":
+        got["victim"] = stale_min_victims(a, rnd, k)
+        return None if got["victim"] is None else got
+    if kind == "other_limit":  # the rows of the other limit under this one's name
+        lo, hi = qr.LIMITS
+        got["room"] = {lo: {u: dict(r, limit=lo) for u, r in got["room"][hi].items()},
+                       hi: {u: dict(r, limit=hi) for u, r in got["room"][lo].items()}}
+        return got
+    if kind == "wrong_order":  # each task answered with its neighbour's row
+        def rotate(rows):
+            us = sorted(rows)
+            return {u: dict(rows[v], task=u) for u, v in zip(us, us[1:] + us[:1])}
+        got["task"] = rotate(got["task"])
+        got["room"] = {lim: rotate(rows) for lim, rows in got["room"].items()}
+        return got
+    raise ValueError(kind)
+
+
+@pytest.mark.parametrize("kind", STALE)
+def test_comparator_notices_a_stale_session(refs, kind):
+    noticed, tried = [], 0
+    for case, c in refs.items():
+        for a, rnd in steps(c):
+            aff = ts.has_pod_affinity(rnd.fx)
+            for k in range(len(rnd.refs.points)):
+                got = stale_rows(kind, a, rnd, k)
+                if got is None:
+                    continue
+                tried += 1
+                for rows in got["room"].values():  # (the references do not say the flag; the comparator asks for it)
+                    for r in rows.values():
+                        r.setdefault("affinity_now", aff)
+                errs, said = qr.compare_point(rnd.refs.points[k], got, aff, case)
+                assert said > 0
+                if errs:
+                    noticed.append(case)
+    print(f"{kind}: noticed on {len(set(noticed))} cases of {tried} points tried")
+    assert noticed, f"the comparator notices {kind} on no case"
+
+
+def test_comparator_passes_the_references_themselves(refs):
+    said = 0
+    for case, c in refs.items():
+        for a, rnd in steps(c):
+            aff = ts.has_pod_affinity(rnd.fx)
+            for pt in rnd.refs.points:
+                got = copy.deepcopy(qr.point_as_rows(pt))
+                for rows in (got["room"] or {}).values():
+                    for r in rows.values():
+                        r.setdefault("affinity_now", aff)
+                errs, n = qr.compare_point(pt, got, aff, case)
+                assert not errs, errs[:5]
+                said += n
+    print(f"{said} reference rows compared with themselves")
+    assert said > 0
