@@ -789,6 +789,69 @@ typedef struct kbg_task_room {
  * KBG_E_UNSUPPORTED over a communicator or without a device. The call changes
  * nothing: every later action returns what it would have. */
 kbg_status kbg_task_headroom(kbg_session* s, const int32_t* tasks, int32_t n_tasks, int32_t limit, kbg_task_room* out);
+
+/* Where a job's Pending tasks would land now (additive within KBG_ABI_VERSION
+ * 13): "would this gang start if allocate reached it now, and if not, which
+ * pod is in the way". Each named job is walked alone from the session as it is
+ * now; jobs do not see each other's hypothetical placements. A job's Pending
+ * tasks with a request (BestEffort ones are backfill's, allocate.go:88-96) are
+ * taken in TaskOrderFn order, the first `limit` of them, against a view of
+ * every live node that is private to the job: Idle, Releasing, pod count, used
+ * host ports, held pod keys. For each task the nodes are taken in index order
+ * and the task goes to the first node that (allocate.go:119-162,
+ * node_info.go:101-129, session.go:205-293)
+ *   passes the predicates plugin against the view (pod cap maxtasks > ntasks,
+ *   selector and affinity, host ports, unschedulable, taints; pod affinity as
+ *   of now; with the plugin off no stage and no pod cap applies), and has
+ *   Resreq.LessEqual(Idle):      an Allocate: Idle.Sub(Resreq), ntasks + 1, the
+ *                                pod's host ports join the node's; or else, on
+ *                                that same node before any later node,
+ *   Resreq.LessEqual(Releasing): a Pipeline: Releasing.Sub(Resreq), ntasks + 1.
+ * LessEqual is the reference's fp64 test with its tolerance and Sub a plain
+ * subtraction per placement, as in kbg_task_headroom. A task no node takes is
+ * reported with node -1 and the walk goes on with the next task
+ * (allocate.go:170). A placement whose PodKey the node's view already holds is
+ * reported and leaves the view unchanged (node_info.go:101-106). A nil-Node
+ * node takes nothing. The queue is not consulted: queue_overused reports it.
+ * In a session with pod affinity today's verdict is applied to every step;
+ * what the walked pods would do to each other's (anti)affinity is not modelled
+ * (kbg_task_headroom's rule), and affinity_now is 1. */
+#define KBG_FIT_MAX_LIMIT 512
+typedef struct kbg_job_fit {
+  int32_t valid;            /* 0: the job has no Pending task with a request now; nothing below is set */
+  int32_t job;
+  int32_t pending;          /* its Pending tasks with a request now */
+  int32_t walked;           /* min(pending, limit): the first tasks in TaskOrderFn order */
+  int32_t placed_idle;      /* walked tasks that would be Allocate decisions */
+  int32_t placed_releasing; /* ... Pipeline decisions */
+  int32_t first_unplaced;   /* the first walked task no node takes (task index), -1 when none */
+  int32_t nodes_used;       /* distinct nodes taking at least one */
+  int32_t ready_num;        /* gang readyTaskNum now (gang.go:44-55; Pipelined counts) */
+  int32_t min_available;
+  int32_t ready_after;      /* walked steps after which ready_num + placed so far >= min_available:
+                               0 = ready now, -1 = not within the walk */
+  int32_t queue_overused;   /* as kbg_task_why: allocate would skip the queue now */
+  int32_t affinity_now;     /* the session has pod affinity: today's verdict is applied to every step */
+  int32_t panic_nodes;      /* live nil-Node nodes: they take nothing */
+  int32_t place_off;        /* index of its first entry in `places`, -1 when places == NULL */
+  int32_t reserved[1];
+} kbg_job_fit_row; /* (C keeps function and typedef names in one name space: the tag is the call's name) */
+typedef struct kbg_fit_place {
+  int32_t task, node /* -1: nowhere */, kind /* KBG_KIND_* (ALLOCATE with node -1) */, reserved;
+} kbg_fit_place;
+/* out[i] describes jobs[i]; jobs == NULL describes every job (n_jobs must be
+ * the job count), as in kbg_victim_reasons; a job index out of range and a
+ * limit outside [1, KBG_FIT_MAX_LIMIT] are KBG_E_INVALID. `places` receives
+ * the walked tasks of all the jobs, each job's `walked` entries in walk order
+ * from its place_off; *n_places is their number. places == NULL with
+ * places_cap == 0 gives the rows only; too small a places_cap is
+ * KBG_E_CAPACITY with *n_places set to the need. Everything else as
+ * kbg_task_headroom: legal any time after open on a session opened with
+ * kbg_options.reasons, KBG_E_UNSUPPORTED over a communicator or without a
+ * device; before the cycle's first action the session is its snapshot. The
+ * call changes nothing: every later action returns what it would have. */
+kbg_status kbg_job_fit(kbg_session* s, const int32_t* jobs, int32_t n_jobs, int32_t limit, kbg_job_fit_row* out,
+                       kbg_fit_place* places, int32_t places_cap, int32_t* n_places);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

@@ -530,4 +530,75 @@ hipError_t launch_task_headroom_init(int32_t* out, int32_t n_shapes, hipStream_t
 hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
                                 hipEvent_t stop = nullptr);
 
+// Where a job's Pending tasks would land now (kbg_job_fit). Each of n_jobs
+// jobs is a walk of steps job_off[j] .. job_off[j + 1], at most kFitMaxSteps,
+// taken in order against a view of the table range that is private to the job
+// and starts as the table is. A step is a shape (TaskShape, never BestEffort).
+// It goes to the lowest node of the range whose `live` bit is set, which
+// passes the static stages against the view as in launch_task_headroom
+// (cap_check: ntasks < maxtasks, sel_ok set, unsched clear, taint_ok set;
+// cap_check 0: every live node passes) and on which
+//   LE(req, Idle)        -> kind 0 (Allocate):  Idle -= req, ntasks += 1
+//   else LE(req, Releasing) -> kind 1 (Pipeline): Releasing -= req, ntasks += 1
+// (allocate.go:119-162: the Releasing test of a node comes before the Idle
+// test of the next; node_info.go:101-129). LE is the reference's
+// `r < x || |x - r| < min` per dimension, the subtraction plain fp64. A step
+// no node takes leaves the view as it is, and the walk goes on
+// (allocate.go:170). out[2 * step] is the global node or -1, out[2 * step + 1]
+// the kind (0 with node -1).
+// `prev` is the index within the job's walk of the previous step of the same
+// shape, or -1: the scan starts at the node that step landed on, inclusive,
+// and a step whose prev landed nowhere lands nowhere without a scan. Inside a
+// walk the view only loses Idle and Releasing and only gains pods, so with a
+// request without a negative dimension a node that turned a shape away keeps
+// turning it away: the cursor changes no result. A shape with a negative
+// request dimension must come with prev = -1 on every step.
+// The node table and the planes are read only. h_shapes, h_steps and h_job_off
+// are the host's copies of the three staged arrays: the launcher reads them
+// and refuses (hipErrorInvalidValue, nothing launched) a job of more than
+// kFitMaxSteps steps, a shape index outside n_shapes, a BestEffort shape, a
+// prev that is not an earlier step of the same job and shape, and a table
+// range of more than kFitMaxNodes nodes (the kernel's touched-word bitmap).
+// n_jobs <= 0 or tab_n <= 0 is a successful no-op.
+constexpr int32_t kFitMaxSteps = 512;
+constexpr int32_t kFitMaxNodes = 1 << 20;
+struct JobFitStep {
+  int32_t shape, prev;
+};
+struct JobFitArgs {
+  const double* nodes;  // the node table block (FirstFitArgs.nodes)
+  int32_t stride, W, tab_lo, tab_n;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const TaskShape* shapes;                             // [n_shapes] staged in device memory
+  const JobFitStep* steps;                             // [job_off[n_jobs]] staged in device memory
+  const int32_t* job_off;                              // [n_jobs + 1] staged in device memory
+  int32_t n_shapes, n_jobs, cap_check;
+  int32_t* out;  // [job_off[n_jobs]][2]
+  const TaskShape* h_shapes;
+  const JobFitStep* h_steps;
+  const int32_t* h_job_off;
+};
+// What launch_job_fit refuses, named; nullptr for a legal launch.
+inline const char* job_fit_refusal(const JobFitArgs& a) {
+  if (a.tab_n > kFitMaxNodes) return "table range past the touched-word bitmap";
+  if (a.n_jobs <= 0 || a.tab_n <= 0) return nullptr;
+  if (!a.h_shapes || !a.h_steps || !a.h_job_off) return "null host copy";
+  if (a.h_job_off[0] != 0) return "job_off does not start at 0";
+  for (int32_t j = 0; j < a.n_jobs; ++j) {
+    const int32_t s0 = a.h_job_off[j], ns = a.h_job_off[j + 1] - s0;
+    if (ns < 0) return "job_off descends";
+    if (ns > kFitMaxSteps) return "a job of more than 512 steps";
+    for (int32_t i = 0; i < ns; ++i) {
+      const JobFitStep& st = a.h_steps[s0 + i];
+      if (st.shape < 0 || st.shape >= a.n_shapes) return "shape index outside n_shapes";
+      if (a.h_shapes[st.shape].flags & kTaskShapeBestEffort) return "a BestEffort shape";
+      if (st.prev < -1 || st.prev >= i || (st.prev >= 0 && a.h_steps[s0 + st.prev].shape != st.shape))
+        return "prev is not an earlier step of the same job and shape";
+    }
+  }
+  return nullptr;
+}
+hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
+                          hipEvent_t stop = nullptr);
+
 }  // namespace kbg

@@ -1747,6 +1747,122 @@ hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEv
   return hipGetLastError();
 }
 
+// ------------------------------------------------------- job fit walk
+// kbg_job_fit: where the Pending tasks of a job would land one after the
+// other (kbg_device.hpp JobFitArgs). One wave per job and one wave per
+// workgroup: the walk is serial, every step sees what the steps before it
+// took. A lane per node of the current 64-node word; the loads, the stage mask
+// on the scalar unit and the LessEqual ballots are kbg_task_headroom_kernel's,
+// and the first fit of a word is the lowest bit of one ballot.
+// The job's view is an overlay in LDS of the nodes its walk has touched, at
+// most one entry per step (kFitMaxSteps of 56 B: the table row, Idle,
+// Releasing, the pod count), and a bitmap of the touched words, one bit per
+// 64-node word of the table range (kFitMaxNodes / 64 bits, 2 KiB). An
+// untouched word is read from the table alone. In a touched word the lanes
+// first look through the overlay, 64 entries at a time, and leave each entry's
+// index in the slot of its lane; a lane with a slot takes its values from
+// there. 32.3 KiB of LDS whatever the node count.
+// The workgroup is one wave, so nothing here is a workgroup barrier: LDS
+// accesses of a wave complete in order, and fit_lds_order keeps the compiler
+// from moving them across the points where lanes read what other lanes wrote.
+__device__ __forceinline__ void fit_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+__global__ __launch_bounds__(64) void kbg_job_fit_kernel(JobFitArgs a) {
+  __shared__ double s_val[kFitMaxSteps * 6];  // Idle c/m/g, Releasing c/m/g of an entry
+  __shared__ int32_t s_row[kFitMaxSteps];     // its table row
+  __shared__ int32_t s_nt[kFitMaxSteps];      // its pod count
+  __shared__ int32_t s_land[kFitMaxSteps];    // the table row each step landed on, -1 nowhere
+  __shared__ uint32_t s_touched[kFitMaxNodes / 64 / 32];
+  __shared__ int32_t s_slot[64];
+  const int lane = threadIdx.x;
+  const int j = blockIdx.x;
+  const int s0 = __builtin_amdgcn_readfirstlane(a.job_off[j]);
+  const int ns = min(__builtin_amdgcn_readfirstlane(a.job_off[j + 1]) - s0, kFitMaxSteps);
+  const int words = (a.tab_n + 63) >> 6;
+  for (int i = lane; i < (words + 31) >> 5; i += 64) s_touched[i] = 0u;
+  fit_lds_order();
+  const size_t L = (size_t)a.stride;
+  const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * L);
+  int n_ov = 0;  // overlay entries (wave-uniform)
+  for (int i = 0; i < ns; ++i) {
+    const int si = __builtin_amdgcn_readfirstlane(a.steps[s0 + i].shape);
+    const int prev = __builtin_amdgcn_readfirstlane(a.steps[s0 + i].prev);
+    const int cls = __builtin_amdgcn_readfirstlane(a.shapes[si].cls);
+    const double q0 = a.shapes[si].req[0], q1 = a.shapes[si].req[1], q2 = a.shapes[si].req[2];
+    // the cursor: this shape's previous step, inclusive; nowhere stays nowhere
+    const int from = prev >= 0 ? __builtin_amdgcn_readfirstlane(s_land[prev]) : 0;
+    int land = -1, kind = 0;
+    for (int wl = from >> 6; from >= 0 && wl < words; ++wl) {
+      const int w = (a.tab_lo >> 6) + wl;           // the global word
+      const int row = wl * 64 + lane;
+      const int r = min(row, a.tab_n - 1);          // a legal row for the ragged word's lanes
+      double ic = a.nodes[r], im = a.nodes[L + r], ig = a.nodes[2 * L + r];
+      double rc = a.nodes[3 * L + r], rm = a.nodes[4 * L + r], rg = a.nodes[5 * L + r];
+      int32_t nt = ni[r];
+      const int32_t mt = ni[L + r];
+      int slot = -1;
+      if ((__builtin_amdgcn_readfirstlane(s_touched[wl >> 5]) >> (wl & 31)) & 1u) {  // (wave-uniform)
+        s_slot[lane] = -1;
+        fit_lds_order();
+        for (int e = lane; e < n_ov; e += 64)
+          if ((s_row[e] >> 6) == wl) s_slot[s_row[e] & 63] = e;  // (a node has one entry at most)
+        fit_lds_order();
+        slot = s_slot[lane];
+        if (slot >= 0) {
+          ic = s_val[slot * 6], im = s_val[slot * 6 + 1], ig = s_val[slot * 6 + 2];
+          rc = s_val[slot * 6 + 3], rm = s_val[slot * 6 + 4], rg = s_val[slot * 6 + 5];
+          nt = s_nt[slot];
+        }
+      }
+      uint64_t valid = a.live[w];
+      if (wl * 64 + 64 > a.tab_n) valid &= (1ull << (a.tab_n - wl * 64)) - 1ull;  // bits past the table's last node
+      if (wl == (from >> 6)) valid &= ~0ull << (from & 63);                        // nodes before the cursor
+      uint64_t pass = valid;
+      if (a.cap_check) {  // predicates.go:125-183
+        pass &= ~__ballot(nt >= mt) & ~a.unsched[w];
+        pass &= a.sel_ok[(size_t)cls * a.W + w] & a.taint_ok[(size_t)cls * a.W + w];
+      }
+      if (!pass) continue;  // (wave-uniform)
+      const uint64_t fi = fit_mask<false>(ic, im, ig, q0, q1, q2);
+      const uint64_t fr = fit_mask<false>(rc, rm, rg, q0, q1, q2);
+      const uint64_t cand = pass & (fi | fr);
+      if (!cand) continue;
+      const int b = __builtin_ctzll(cand);
+      kind = (fi >> b) & 1ull ? 0 : 1;  // Idle first, else Releasing on the same node (allocate.go:136-162)
+      const uint64_t has = __ballot(slot >= 0);
+      const int e = (has >> b) & 1ull ? __builtin_amdgcn_readlane(slot, b) : n_ov++;
+      if (lane == b) {
+        if (kind == 0) ic -= q0, im -= q1, ig -= q2;  // Idle.Sub (node_info.go:108-118)
+        else rc -= q0, rm -= q1, rg -= q2;            // Releasing.Sub (node_info.go:119-126)
+        s_row[e] = row;
+        s_val[e * 6] = ic, s_val[e * 6 + 1] = im, s_val[e * 6 + 2] = ig;
+        s_val[e * 6 + 3] = rc, s_val[e * 6 + 4] = rm, s_val[e * 6 + 5] = rg;
+        s_nt[e] = nt + 1;
+      }
+      if (lane == 0) s_touched[wl >> 5] |= 1u << (wl & 31);
+      land = wl * 64 + b;
+      break;
+    }
+    if (lane == 0) {
+      s_land[i] = land;
+      a.out[2 * (size_t)(s0 + i)] = land < 0 ? -1 : a.tab_lo + land;
+      a.out[2 * (size_t)(s0 + i) + 1] = kind;
+    }
+    fit_lds_order();
+  }
+}
+
+hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (job_fit_refusal(a)) return hipErrorInvalidValue;
+  if (a.n_jobs <= 0 || a.tab_n <= 0) return hipSuccess;
+  hipExtLaunchKernelGGL(kbg_job_fit_kernel, dim3(a.n_jobs), dim3(64), 0, stream, start, stop, 0, a);
+  return hipGetLastError();
+}
+
 __device__ __forceinline__ void apply_node_delta(const NodeSoA& nd, const NodeDelta& x) {
   nd.idle_cpu[x.node] = x.idle[0];
   nd.idle_mem[x.node] = x.idle[1];

@@ -779,6 +779,10 @@ void free_device(Session& S) {
   S.d_room_shapes = nullptr;  // (d_allocs too)
   S.d_room_out = nullptr;
   S.room_cap = 0;
+  S.d_fit_shapes = nullptr;  // (d_allocs too)
+  S.d_fit_steps = nullptr;
+  S.d_fit_off = S.d_fit_out = nullptr;
+  S.fit_shape_cap = S.fit_step_cap = S.fit_job_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1098,6 +1102,8 @@ kbg_status device_scan(Session& S, kbg::Stage& sg, int32_t G, int32_t base) {
 #include "kbg_task_why.ipp"  // kbg_task_reasons: why a Pending task would not be placed now
 
 #include "kbg_headroom.ipp"  // kbg_task_headroom: how many copies of a Pending task fit now
+
+#include "kbg_job_fit.ipp"  // kbg_job_fit: where a job's Pending tasks would land now
 
 #include "kbg_update.ipp"  // resident session updates (kbg_session_update)
 
@@ -1464,6 +1470,19 @@ kbg_status kbg_task_headroom(kbg_session* s, const int32_t* tasks, int32_t n_tas
   if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
   try {
     return task_headroom(s->s, tasks, n_tasks, limit, out);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
+}
+
+kbg_status kbg_job_fit(kbg_session* s, const int32_t* jobs, int32_t n_jobs, int32_t limit, kbg_job_fit_row* out,
+                       kbg_fit_place* places, int32_t places_cap, int32_t* n_places) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return job_fit(s->s, jobs, n_jobs, limit, out, places, places_cap, n_places);
   } catch (const std::bad_alloc&) {
     return fail(KBG_E_NOMEM, "host allocation failed");
   } catch (const std::exception& e) {

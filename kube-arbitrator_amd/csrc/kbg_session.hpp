@@ -587,6 +587,11 @@ struct Session {
   kbg::TaskShape* d_room_shapes = nullptr;
   int32_t* d_room_out = nullptr;
   size_t room_cap = 0;                                // shapes both hold
+  // kbg_job_fit: the staged shapes, steps, job offsets and the places (HBM, grown on demand)
+  kbg::TaskShape* d_fit_shapes = nullptr;
+  kbg::JobFitStep* d_fit_steps = nullptr;
+  int32_t *d_fit_off = nullptr, *d_fit_out = nullptr;
+  size_t fit_shape_cap = 0, fit_step_cap = 0, fit_job_cap = 0;
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while

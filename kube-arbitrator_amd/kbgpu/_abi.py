@@ -197,6 +197,21 @@ class kbg_task_room(ctypes.Structure):
                 ("affinity_now", i32), ("panic_nodes", i32), ("reserved", i32 * 1)]
 
 
+# kbg_job_fit: the largest limit a call may name (KBG_FIT_MAX_LIMIT)
+FIT_MAX_LIMIT = 512
+
+
+class kbg_job_fit(ctypes.Structure):
+    _fields_ = [("valid", i32), ("job", i32), ("pending", i32), ("walked", i32), ("placed_idle", i32),
+                ("placed_releasing", i32), ("first_unplaced", i32), ("nodes_used", i32), ("ready_num", i32),
+                ("min_available", i32), ("ready_after", i32), ("queue_overused", i32), ("affinity_now", i32),
+                ("panic_nodes", i32), ("place_off", i32), ("reserved", i32 * 1)]
+
+
+class kbg_fit_place(ctypes.Structure):
+    _fields_ = [("task", i32), ("node", i32), ("kind", i32), ("reserved", i32)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -290,6 +305,7 @@ SIGNATURES = {
     "kbg_victim_reasons": (i32, [ctypes.c_void_p, i32, P(i32), i32, P(kbg_victim_why)]),
     "kbg_task_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_task_why)]),
     "kbg_task_headroom": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_task_room)]),
+    "kbg_job_fit": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_job_fit), P(kbg_fit_place), i32, P(i32)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -118,6 +118,29 @@ def headroom_message(row, needed):
             f"resources ({nodes} nodes){tail}")
 
 
+def job_fit_message(row):
+    """One line for a job that is not ready (a Session.job_fit row): how many
+    of its next pending pods fit now, from Idle and from resources that are
+    being released, on how many nodes, and either the pod after which the gang
+    has enough or the first task without room."""
+    if not row["valid"]:
+        return "nothing pending"
+    needed = max(0, row["min_available"] - row["ready_num"])
+    placed = row["placed_idle"] + row["placed_releasing"]
+    if row["ready_after"] >= 0:
+        end = f"enough after pod {row['ready_after']}"
+    elif row["first_unplaced"] >= 0:
+        end = f"not enough, first without room: task {row['first_unplaced']}"
+    else:
+        end = "not enough"
+    tail = f", {row['pending'] - row['walked']} not walked" if row["pending"] > row["walked"] else ""
+    tail += " (pod affinity as it is now)" if row["affinity_now"] else ""
+    tail += " (its queue is overused)" if row["queue_overused"] else ""
+    return (f"needs {needed} more; {placed} of its next {row['walked']} pending pods fit now "
+            f"({row['placed_idle']} on idle, {row['placed_releasing']} on releasing resources, "
+            f"{row['nodes_used']} nodes): {end}{tail}")
+
+
 def reasons_row(st):
     """A kbg_job_reasons as the output rows carry it."""
     return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),

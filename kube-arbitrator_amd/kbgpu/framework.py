@@ -627,6 +627,34 @@ class Session:
                  "max_node_copies": r.max_node_copies, "limit_hit": r.limit_hit, "affinity_now": bool(r.affinity_now),
                  "panic_nodes": r.panic_nodes} for r in out[:n]]
 
+    def job_fit(self, jobs=None, limit=_abi.FIT_MAX_LIMIT):
+        """One dict per job (the indices `jobs`, or every job): where its
+        Pending tasks with a request, the first `limit` (1..512) in
+        TaskOrderFn order, would land now, each on its first fitting node of a
+        view in which the tasks before it have taken their share
+        (kbg_job_fit). `places` holds (task, node, kind) per walked task, node
+        -1 for a task no node takes. Legal any time after open on sessions
+        opened with reasons=True; changes nothing."""
+        if jobs is None:
+            n, arr = len(self.jobs), None
+        else:
+            n, arr = len(jobs), (ctypes.c_int32 * max(len(jobs), 1))(*jobs)
+        out = (_abi.kbg_job_fit * max(n, 1))()
+        need = ctypes.c_int32(0)
+        _abi.check(_abi.lib().kbg_job_fit(self.handle, arr, n, int(limit), out, None, 0, ctypes.byref(need)))
+        places = (_abi.kbg_fit_place * max(need.value, 1))()
+        _abi.check(_abi.lib().kbg_job_fit(self.handle, arr, n, int(limit), out, places, need.value, ctypes.byref(need)))
+        keys = ("job", "pending", "walked", "placed_idle", "placed_releasing", "first_unplaced", "nodes_used",
+                "ready_num", "min_available", "ready_after", "panic_nodes")
+        rows = []
+        for r in out[:n]:
+            row = {"valid": bool(r.valid), **{k: getattr(r, k) for k in keys},
+                   "queue_overused": bool(r.queue_overused), "affinity_now": bool(r.affinity_now), "places": []}
+            if r.valid:
+                row["places"] = [(p.task, p.node, p.kind) for p in places[r.place_off:r.place_off + r.walked]]
+            rows.append(row)
+        return rows
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))

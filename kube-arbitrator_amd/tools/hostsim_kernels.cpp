@@ -11,7 +11,8 @@
 // tests/test_hostsim_victim_why.py does so for the victim-reasons launchers
 // (tests/victim_why_ref.py), tests/test_hostsim_task_why.py for the
 // pending-task reasons (tests/task_why_ref.py), tests/test_hostsim_headroom.py
-// for the pending-task headroom (tests/headroom_ref.py).
+// for the pending-task headroom (tests/headroom_ref.py),
+// tests/test_hostsim_job_fit.py for the job fit walk (tests/job_fit_ref.py).
 //
 // The victim launchers count their launches (kbg_hostsim_launch_counts, an
 // export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
@@ -691,6 +692,54 @@ void task_headroom_run(const TaskRoomArgs& a) {
   }
 }
 
+// ---- job fit walk (kbg_device.hpp JobFitArgs): every job's steps in order
+// against a view of its own, a map of the rows its walk has touched. The
+// cursor is the device's: a step starts at the row its prev landed on.
+void job_fit_run(const JobFitArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  struct View {
+    double idle[3], rel[3];
+    int32_t nt;
+  };
+  for (int32_t j = 0; j < a.n_jobs; ++j) {
+    const int32_t s0 = a.job_off[j], ns = a.job_off[j + 1] - s0;
+    std::map<int32_t, View> view;
+    std::vector<int32_t> land(ns, -1);
+    for (int32_t i = 0; i < ns; ++i) {
+      const JobFitStep& st = a.steps[s0 + i];
+      const TaskShape& sh = a.shapes[st.shape];
+      int32_t at = -1, kind = 0;
+      const int32_t from = st.prev >= 0 ? land[st.prev] : 0;
+      for (int32_t row = from; from >= 0 && row < a.tab_n; ++row) {
+        const int32_t n = a.tab_lo + row;
+        const uint64_t bit = 1ull << (n & 63);
+        if (!(a.live[n >> 6] & bit)) continue;
+        View v{{t.ic[row], t.im[row], t.ig[row]}, {t.rc[row], t.rm[row], t.rg[row]}, t.nt[row]};
+        const auto it = view.find(row);
+        if (it != view.end()) v = it->second;
+        if (a.cap_check) {  // predicates.go:125-183
+          if (v.nt >= t.mt[row]) continue;
+          if (!(a.sel_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) continue;
+          if (a.unsched[n >> 6] & bit) continue;
+          if (!(a.taint_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) continue;
+        }
+        double* x = nullptr;
+        if (fits(false, sh.req, v.idle[0], v.idle[1], v.idle[2])) x = v.idle, kind = 0;  // allocate.go:136-146
+        else if (fits(false, sh.req, v.rel[0], v.rel[1], v.rel[2])) x = v.rel, kind = 1;  // allocate.go:148-162
+        if (!x) continue;
+        for (int d = 0; d < 3; ++d) x[d] -= sh.req[d];
+        v.nt++;
+        view[row] = v;
+        at = row;
+        break;
+      }
+      land[i] = at;
+      a.out[2 * (size_t)(s0 + i)] = at < 0 ? -1 : a.tab_lo + at;
+      a.out[2 * (size_t)(s0 + i) + 1] = at < 0 ? 0 : kind;
+    }
+  }
+}
+
 void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
   n.idle_cpu[d.node] = d.idle[0];
   n.idle_mem[d.node] = d.idle[1];
@@ -730,11 +779,12 @@ enum Count : int {
   kCountTaskHeadroom,
   kCountStageMask,
   kCountVictimWhy,
+  kCountJobFit,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,victim_why";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,victim_why,job_fit";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -926,6 +976,13 @@ hipError_t launch_task_headroom(const TaskRoomArgs& a, hipStream_t stream, hipEv
   if (a.n_shapes <= 0 || a.tab_n <= 0) return hipSuccess;
   g_count[kCountTaskHeadroom]++;
   return launch(stream, start, stop, [a] { task_headroom_run(a); });
+}
+
+hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (job_fit_refusal(a)) return hipErrorInvalidValue;
+  if (a.n_jobs <= 0 || a.tab_n <= 0) return hipSuccess;
+  g_count[kCountJobFit]++;
+  return launch(stream, start, stop, [a] { job_fit_run(a); });
 }
 
 }  // namespace kbg

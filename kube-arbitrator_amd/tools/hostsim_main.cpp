@@ -5,7 +5,7 @@
 //
 //   hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions a,b,...]
 //                [--batch-tasks N] [--candidates N] [--full-scan]
-//                [--general-scan] [--repeat N] [--victim-reasons]
+//                [--general-scan] [--repeat N] [--victim-reasons] [--job-fit]
 //
 // Each repeat opens a session, runs the actions (reclaim, allocate, backfill,
 // preempt, in the order given), resets the session, runs them again and
@@ -17,6 +17,10 @@
 // kbg_victim_reasons for every job in all three modes after reclaim and after
 // preempt. The rows do not go to OUT (the call changes nothing, so OUT is the
 // same file with and without the flag); a summary goes to stderr.
+// --job-fit opens the session with kbg_options.reasons too and calls
+// kbg_job_fit for every job before the first action and after each one (once
+// per action prefix), at limit 512 with the places and at limit 2 without. The
+// rows do not go to OUT either; a summary goes to stderr.
 // Exit status 0 unless the arguments or the files are unusable.
 #include <cstdio>
 #include <cstdlib>
@@ -68,10 +72,39 @@ void victim_reasons(kbg_session* s, const std::string& after, int32_t n_jobs) {
   }
 }
 
+// kbg_job_fit of every job; what it found, to stderr.
+void job_fit(kbg_session* s, const std::string& after, int32_t n_jobs) {
+  std::vector<kbg_job_fit_row> rows((size_t)n_jobs + 1);
+  int32_t need = 0;
+  kbg_status st = kbg_job_fit(s, nullptr, n_jobs, 2, rows.data(), nullptr, 0, &need);
+  std::vector<kbg_fit_place> places;
+  if (st == KBG_OK && (st = kbg_job_fit(s, nullptr, n_jobs, KBG_FIT_MAX_LIMIT, rows.data(), nullptr, 0, &need)) == KBG_OK) {
+    places.resize((size_t)need + 1);
+    st = kbg_job_fit(s, nullptr, n_jobs, KBG_FIT_MAX_LIMIT, rows.data(), places.data(), need, &need);
+  }
+  if (st != KBG_OK) {
+    fprintf(stderr, "hostsim_main: job fit after %s: status %d: %s\n", after.c_str(), (int)st, kbg_last_error());
+    return;
+  }
+  int64_t valid = 0, idle = 0, rel = 0, nowhere = 0, ready = 0;
+  for (int32_t j = 0; j < n_jobs; ++j) {
+    if (!rows[j].valid) continue;
+    ++valid;
+    idle += rows[j].placed_idle;
+    rel += rows[j].placed_releasing;
+    ready += rows[j].ready_after >= 0;
+    for (int32_t k = 0; k < rows[j].walked; ++k) nowhere += places[(size_t)rows[j].place_off + k].node < 0;
+  }
+  fprintf(stderr, "hostsim_main: job fit after %s: %lld jobs with a Pending task, %lld steps on idle, %lld on releasing, "
+                  "%lld nowhere; %lld jobs get ready\n",
+          after.c_str(), (long long)valid, (long long)idle, (long long)rel, (long long)nowhere, (long long)ready);
+}
+
 void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
-                 std::vector<char>& out, int32_t why_jobs = -1) {
+                 std::vector<char>& out, int32_t why_jobs = -1, int32_t fit_jobs = -1) {
   std::vector<kbg_decision> dec((size_t)n_tasks + 1);
   int32_t n = 0;
+  if (fit_jobs >= 0) job_fit(s, "open", fit_jobs);
   for (const std::string& a : actions) {
     const kbg_status st = run_action(s, a, dec.data(), (int32_t)dec.size(), &n);
     put_i32(out, (int32_t)st);
@@ -81,6 +114,7 @@ void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_
       return;
     }
     if (why_jobs >= 0 && (a == "reclaim" || a == "preempt")) victim_reasons(s, a, why_jobs);
+    if (fit_jobs >= 0) job_fit(s, a, fit_jobs);
   }
   // the decision log (Allocate and Pipeline decisions of every action) and the action behind each
   put_i32(out, n);
@@ -109,7 +143,7 @@ int usage() {
   fprintf(stderr,
           "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions reclaim,allocate,backfill,preempt]\n"
           "                    [--batch-tasks N] [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n"
-          "                    [--victim-reasons]\n"
+          "                    [--victim-reasons] [--job-fit]\n"
           "  --actions: any of reclaim, allocate, backfill, preempt, run in the order given (default allocate)\n");
   return 2;
 }
@@ -122,7 +156,7 @@ int main(int argc, char** argv) {
   memset(&opts, 0, sizeof opts);
   std::vector<std::string> actions{"allocate"};
   int repeat = 1;
-  bool why = false;
+  bool why = false, fit = false;
   for (int i = 3; i < argc; ++i) {
     const std::string a = argv[i];
     const bool more = i + 1 < argc;
@@ -152,6 +186,9 @@ int main(int argc, char** argv) {
     } else if (a == "--victim-reasons") {
       why = true;
       opts.reasons = 1;
+    } else if (a == "--job-fit") {
+      fit = true;
+      opts.reasons = 1;
     } else if (a == "--repeat" && more) {
       repeat = atoi(argv[++i]);
     } else {
@@ -173,10 +210,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "hostsim_main: open: status %d: %s\n", (int)st, kbg_last_error());
       continue;
     }
-    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1);
+    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1);
     const kbg_status rs = kbg_session_reset(s);
     put_i32(out, (int32_t)rs);
-    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1);
+    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1);
     kbg_session_close(s);
   }
   kbg_snapshot_blob_free(blob);
