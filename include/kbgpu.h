@@ -506,14 +506,26 @@ enum {
                               pods on it; their tasks stay in their jobs, on no node (NodeName unchanged) */
   KBG_EV_JOB_ADD = 8,      /* cache.AddPodGroup of a new job (event_handlers.go:344-358, setPodGroup): JobID
                               `name`, queue index `queue`, `min_available`, `creation_ns`, `priority`; it joins
-                              ssn.Jobs last, its pods follow as KBG_EV_POD_ADD */
+                              ssn.Jobs last, its pods follow as KBG_EV_POD_ADD. The cache's setPodGroup takes up
+                              a JobInfo it still holds (:344-358), with the tasks and the PodGroup or PDB it
+                              kept; the session adopts none of that, so a JobID the session saw leave that way
+                              — deleted (KBG_EV_JOB_DELETE) while it held tasks, or dropped with its queue
+                              (KBG_EV_QUEUE_DELETE) — is refused, in the same batch and in every later update
+                              (KBG_E_UNSUPPORTED: re-open). A job deleted without tasks may be added again */
   KBG_EV_JOB_DELETE = 9,   /* cache.DeletePodGroup (event_handlers.go:361-381, UnsetPodGroup) or DeletePDB
                               (:479-494, UnsetPDB) once the job holds neither: job `job` leaves ssn.Jobs; its
                               pods stay on their nodes as pods outside the session jobs and its Running tasks
                               join Session.Others (cache.go:570-582). While the other is left the job stays
                               in ssn.Jobs as it is: no event */
   KBG_EV_QUEUE_ADD = 10,   /* cache.AddQueue (event_handlers.go:635-640): queue `name` with `weight` joins ssn.Queues
-                              last */
+                              last, without jobs. In the cache every job of sc.Jobs naming the queue is back in
+                              the snapshot with it (cache.go:584-588), so the name of a queue whose
+                              KBG_EV_QUEUE_DELETE dropped jobs is refused from then on, in the same batch and
+                              in every later update (KBG_E_UNSUPPORTED: re-open; also when the caller has since
+                              deleted those jobs' PodGroups, which the session cannot see). A queue deleted
+                              without jobs may be added again. A queue new to the session that jobs outside
+                              the snapshot name (their queue was missing at open) is the caller's to notice:
+                              re-open */
   KBG_EV_QUEUE_DELETE = 11, /* cache.DeleteQueue (event_handlers.go:650-654): queue `queue` leaves ssn.Queues, and
                                every job of it leaves ssn.Jobs (cache.go:584-588; not into Others) */
   /* Update events of jobs and queues the session holds. They are additive:
@@ -596,8 +608,18 @@ kbg_status kbg_session_update(kbg_session* s, const kbg_event* events, int32_t n
  * events created. *n_out = the map's length (0: the last update renumbered
  * nothing — every index kept). A structural update rebuilds the session from
  * its own updated snapshot (the cost of an open, without the caller's
- * snapshot); pods that predate their PodGroup or queue (already on a node
- * as pods outside the session jobs) are refused (KBG_E_UNSUPPORTED). */
+ * snapshot). It adopts nothing the cache holds outside the snapshot. What the
+ * library can refuse (KBG_E_UNSUPPORTED, kbg_last_error names the queue or
+ * JobID, the session unchanged) is what it saw: a KBG_EV_QUEUE_ADD of a queue
+ * name whose deletion dropped jobs, a KBG_EV_JOB_ADD of a JobID that left with
+ * its queue or was deleted while it held tasks — the session remembers both
+ * through every rebuild, reset and cycle until it is closed — and a
+ * KBG_EV_POD_ADD of a pod of a new job whose key a pod outside the session
+ * jobs holds on its node (it predates its PodGroup). What it never saw is the
+ * caller's duty: a queue or PodGroup new to the session for jobs or pods the
+ * cache held outside the snapshot at open (a job whose queue was missing,
+ * Pending pods without a PodGroup) needs a re-open. After a refused update
+ * every map is empty (nothing was renumbered). */
 enum { KBG_RENUM_TASKS = 0, KBG_RENUM_NODES = 1, KBG_RENUM_JOBS = 2, KBG_RENUM_QUEUES = 3 };
 kbg_status kbg_session_renumbering(kbg_session* s, int32_t kind, int32_t* out, int32_t cap, int32_t* n_out);
 

@@ -1292,6 +1292,7 @@ kbg_status kbg_session_update(kbg_session* s, const kbg_event* events, int32_t n
   HIP_TRY(hipSetDevice(S.device));
   if (n < 0 || (n > 0 && !events)) return fail(KBG_E_INVALID, "events");
   kbg_status st;
+  for (auto& r : S.renum) r.clear();  // this update's maps: a refused batch renumbers nothing
   try {
     st = update_precheck(S, events, n);
   } catch (const std::bad_alloc&) {

@@ -556,7 +556,15 @@ struct Session {
   std::vector<uint8_t> node_dead, job_dead, queue_dead, job_to_others;
   std::vector<int32_t> queue_next;                    // KBG_EV_QUEUE_UPDATE: dead queue index -> the index it took (-1: none)
   std::vector<int32_t> renum[4];
-  std::vector<kbg_plugin_option> plugins_in;          // the snapshot's tier entries, for the rebuild
+  // Names the session saw leave while the cache keeps what they named
+  // (deleteQueue removes only sc.Queues[uid], deletePodGroup keeps the JobInfo
+  // and its tasks: event_handlers.go:361-381,649-654): a QUEUE_ADD / JOB_ADD of
+  // one would bring jobs or tasks back that the session dropped, and is
+  // refused (update_precheck). Committed when a batch is accepted
+  // (restructure), kept through every rebuild.
+  std::unordered_set<std::string> dropped_queues;     // deleted queues whose jobs left ssn.Jobs with them
+  std::unordered_set<std::string> dropped_jobs;       // jobs that left with their queue, or deleted while holding tasks
+  std::vector<kbg_plugin_option> plugins_in;         // the snapshot's tier entries, for the rebuild
   std::vector<int32_t> tier_sizes_in;
   bool task_ranks_stale = false;                      // tasks were added: re-rank their jobs' UIDs
   std::vector<int32_t> rank_dirty_jobs;

@@ -682,6 +682,34 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
     auto a = have.find(S.canon[id]);
     return a != have.end() && !gone[a->second];
   };
+  // A name that left while the cache keeps what it named (Session::dropped_queues /
+  // dropped_jobs, or kLeft in the batch's overlay): adding it again is refused.
+  constexpr int32_t kLeft = -2;
+  auto left = [&](const std::unordered_map<std::string, int32_t>& batch, const std::unordered_set<std::string>& dropped,
+                  const std::string& nm) {
+    if (auto b = batch.find(nm); b != batch.end()) return b->second == kLeft;
+    return dropped.count(nm) != 0;
+  };
+  auto job_name_of = [&](int32_t j) -> std::string {
+    if (j < S.n_jobs) return S.strs[S.jobs_in[j].uid];
+    for (const auto& [nm, k] : bjobs)
+      if (k == j) return nm;
+    return "";
+  };
+  auto queue_name_of = [&](int32_t q) -> std::string {
+    if (q < S.n_queues) return S.strs[S.queues_in[q].uid];
+    for (const auto& [nm, k] : bqueues)
+      if (k == q) return nm;
+    return "";
+  };
+  auto job_has_tasks = [&](int32_t j) {  // JobInfo.Tasks as the events before this one leave it
+    if (j < S.n_jobs)
+      for (const int32_t t : S.job_task_order[j])
+        if (!dead[t]) return true;
+    for (size_t k = 0; k < add_job.size(); ++k)
+      if (add_job[k] == j && !dead[T0 + k]) return true;
+    return false;
+  };
   auto node_name_of = [&](int32_t nd) -> std::string {  // "" : a pod-only node without a known name
     if (nd >= S.n_nodes) {
       for (const auto& [nm, i] : bnodes)
@@ -852,6 +880,9 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
           return fail(KBG_E_INVALID, "JOB_ADD event (name, queue)");
         if (uid_live(bjobs, job_of_uid, jdead, e.name))
           return fail(KBG_E_INVALID, "JOB_ADD of a JobID the session holds");
+        if (left(bjobs, S.dropped_jobs, e.name))
+          return fail(KBG_E_UNSUPPORTED, std::string("JOB_ADD of job '") + e.name + "': it left the session while the "
+                      "cache kept its PodGroup or its pods, which a PodGroup or PDB set on it now takes up again: re-open");
         bjobs[e.name] = J++;
         jdead.push_back(0);
         jq.push_back(e.queue);
@@ -859,29 +890,35 @@ kbg_status update_precheck(const Session& S, const kbg_event* ev, int32_t n) {
       }
       case KBG_EV_JOB_DELETE:
         if (e.job < 0 || e.job >= J || jdead[e.job]) return fail(KBG_E_INVALID, "JOB_DELETE event job");
+        // the cache keeps the JobInfo and its tasks (deletePodGroup, event_handlers.go:366-380): only a
+        // job without tasks is free to be added again
+        bjobs[job_name_of(e.job)] = job_has_tasks(e.job) ? kLeft : -1;
         jdead[e.job] = 1;
-        for (auto& [nm, j] : bjobs)
-          if (j == e.job) j = -1;
         break;
       case KBG_EV_QUEUE_ADD: {
         if (!e.name || !e.name[0]) return fail(KBG_E_INVALID, "QUEUE_ADD event name");
         if (uid_live(bqueues, queue_of_uid, qdead, e.name))
           return fail(KBG_E_INVALID, "QUEUE_ADD of a queue the session holds");
+        if (left(bqueues, S.dropped_queues, e.name))
+          return fail(KBG_E_UNSUPPORTED, std::string("QUEUE_ADD of queue '") + e.name + "': its jobs left the session "
+                      "when it was deleted, and the cache still holds them (sc.Jobs; cache.go:584-588 filters by "
+                      "queue at Snapshot): re-open");
         bqueues[e.name] = Q++;
         qdead.push_back(0);
         break;
       }
       case KBG_EV_QUEUE_DELETE: {
         if (e.queue < 0 || e.queue >= Q || qdead[e.queue]) return fail(KBG_E_INVALID, "QUEUE_DELETE event queue");
+        const std::string qn = queue_name_of(e.queue);
         qdead[e.queue] = 1;
-        for (auto& [nm, q] : bqueues)
-          if (q == e.queue) q = -1;
-        for (int32_t j = 0; j < J; ++j)  // its jobs leave ssn.Jobs (cache.go:584-588)
+        bool jobs_left = false;
+        for (int32_t j = 0; j < J; ++j)  // its jobs leave ssn.Jobs (cache.go:584-588); sc.Jobs keeps them
           if (!jdead[j] && job_queue_of(j) == e.queue) {
+            bjobs[job_name_of(j)] = kLeft;
             jdead[j] = 1;
-            for (auto& [nm, k] : bjobs)
-              if (k == j) k = -1;
+            jobs_left = true;
           }
+        bqueues[qn] = jobs_left ? kLeft : -1;  // a queue without jobs is free to be added again
         break;
       }
       case KBG_EV_JOB_UPDATE:  // (a batch without structural events has deleted nothing)
@@ -1149,6 +1186,24 @@ kbg_status restructure(Session& S) {
     for (int32_t t = 0; t < R->n_tasks; ++t)
       if (R->task_cnode[t] < 0)
         if (auto it = named.find(R->canon[R->tasks_in[t].node_name]); it != named.end()) R->task_cnode[t] = it->second;
+  // the names that left with this batch join those the session remembers
+  // (the batch is accepted: a refused one never gets here)
+  R->dropped_queues = std::move(S.dropped_queues);
+  R->dropped_jobs = std::move(S.dropped_jobs);
+  for (int32_t j = 0; j < S.n_jobs; ++j) {
+    if (!S.job_dead[j]) continue;
+    const std::string& uid = R->strs[S.jobs_in[j].uid];
+    if (S.job_to_others[j]) {  // JOB_DELETE: the cache's JobInfo keeps its tasks; without any it is free again
+      for (const int32_t t : S.job_task_order[j])
+        if (S.task_live[t]) {
+          R->dropped_jobs.insert(uid);
+          break;
+        }
+    } else {  // it left with its queue, its PodGroup or PDB still set
+      R->dropped_jobs.insert(uid);
+      R->dropped_queues.insert(R->strs[S.queues_in[S.jobs_in[j].queue].uid]);
+    }
+  }
   R->updates = S.updates;
   R->rebuilds = S.rebuilds + 1;
   phase("pod-only names");

@@ -175,6 +175,11 @@ class Session:
         follow the library's renumbering (kbg_session_renumbering). A PodGroup
         or PDB set on a session job (KBG_EV_JOB_UPDATE) and a queue added again
         under a UID the session holds (KBG_EV_QUEUE_SET) change it in place.
+        A queue, PodGroup or PDB that returns for jobs or pods the cache holds
+        outside ssn.Jobs (a deleted queue added again, a PodGroup deleted and
+        set again on a job with pods, a queue that was missing at open) would
+        bring them back in the reference's cache; the session adopts none of
+        them, so marshal raises a ValueError naming the queue or JobID: re-open.
         The wrapper's JobInfo / QueueInfo objects follow the events (pod_group,
         pdb, min_available, queue, weight) once the library took the batch;
         the host-side task and node objects are not replayed: read results
@@ -209,6 +214,14 @@ class Session:
         queue_weights = {}  # session queue index -> its weight after the events
         queue_moved = {}  # queue index a queue_update killed -> the index the queue took
         outside = set()  # JobIDs whose pods stay in the cache outside the session jobs
+        # the cache's jobs outside ssn.Jobs as the events leave them (applied in _accept): a job that
+        # left keeps its JobInfo and its tasks in sc.Jobs (deletePodGroup, event_handlers.go:366-380;
+        # deleteQueue removes only sc.Queues[uid], :649-654), so a queue or PodGroup that returns
+        # brings back what the session dropped
+        away = dict(self._away_jobs())
+        dead_uids = set()  # pods the batch deleted
+        live_delta = {}  # JobID -> pods the batch added minus those it deleted
+        base_live = []  # (lazily) JobID -> its live pods in the wrapper's task list
         default_queue = getattr(self.cache, "default_queue", "")
 
         def ev():
@@ -260,14 +273,47 @@ class Session:
             new_jobs[n_jobs] = job
             n_jobs += 1
 
+        def has_pods(jid):
+            """Whether the cache's JobInfo of session job jid holds tasks now."""
+            if not base_live:
+                gone, count = self._dead_uids(), {}
+                for t in flat.task_objs:
+                    if t is not None and t.uid not in gone:
+                        count[t.job] = count.get(t.job, 0) + 1
+                base_live.append(count)
+            return base_live[0].get(jid, 0) + live_delta.get(jid, 0) > 0
+
         def job_delete(jid):
             """KBG_EV_JOB_DELETE: neither a PodGroup nor a PDB is left (cache.go:570-582)."""
             e = ev()
-            e.kind, e.job = _abi.EV_JOB_DELETE, jidx.pop(jid)
-            outside.add(jid)  # its pods stay in the cache, outside the session jobs
+            e.kind, e.job = _abi.EV_JOB_DELETE, jidx[jid]
+            away[jid] = SimpleNamespace(queue=job_of(jidx[jid]).queue, pod_group=False, pdb=False, pods=has_pods(jid))
+            jidx.pop(jid)
+            if away[jid].pods:
+                outside.add(jid)  # its pods stay in the cache, outside the session jobs
 
         def outside_job(jid):
             return jid in outside or jid in self._outside_jobs()
+
+        def returning_job(jid, what):
+            """A PodGroup or PDB set on a JobID the cache holds outside ssn.Jobs takes up
+            the JobInfo it finds there (setPodGroup, event_handlers.go:344-358): its pods,
+            or the PodGroup / PDB it kept, which the session does not hold."""
+            a = away.get(jid)
+            if a is None:
+                return
+            if a.pods or a.pod_group or a.pdb:
+                raise ValueError(f"{what} {jid!r}: the cache holds that job outside the session jobs (it left the "
+                                 "session, or its queue was missing, and keeps its pods, PodGroup or PDB): re-open")
+            del away[jid]  # a JobInfo without pods, PodGroup or PDB: as good as new
+
+        def returning_queue(name):
+            """A queue that joins brings every cache job naming it into the snapshot
+            (cache.go:584-588): jobs that left with it, or that never had their queue."""
+            for jid, a in away.items():
+                if a.queue == name and (a.pod_group or a.pdb):
+                    raise ValueError(f"queue {name!r}: the cache holds job {jid!r} of that queue outside the session "
+                                     "jobs (it left with the queue, or its queue was missing at open): re-open")
 
         def node_spec(e, obj):
             ni = NodeInfo(obj)
@@ -367,6 +413,8 @@ class Session:
                             job_edit(j).pod_group = None  # it stays in ssn.Jobs, its fields as they are (cache.go:570)
                         else:
                             job_delete(jid)
+                    elif jid in away:
+                        away[jid] = SimpleNamespace(**dict(vars(away[jid]), pod_group=False))
                     continue
                 if jid in jidx:  # setPodGroup on a job the session holds (:344-363): in place
                     job = job_edit(jidx[jid])
@@ -376,6 +424,7 @@ class Session:
                 if outside_job(jid):
                     raise ValueError(f"PodGroup {jid!r}: the cache holds pods of it outside the session jobs "
                                      "(they predate the PodGroup): re-open")
+                returning_job(jid, "PodGroup")
                 job = JobInfo(jid)
                 job.set_pod_group(obj, default_queue)
                 job_add(job)
@@ -391,6 +440,8 @@ class Session:
                             job_edit(j).pdb = None
                         else:
                             job_delete(jid)
+                    elif jid in away:
+                        away[jid] = SimpleNamespace(**dict(vars(away[jid]), pdb=False))
                     continue
                 if jid in jidx:  # setPDB on a job the session holds: in place
                     job = job_edit(jidx[jid])
@@ -400,6 +451,7 @@ class Session:
                 if outside_job(jid):
                     raise ValueError(f"PodDisruptionBudget of {jid!r}: the cache holds pods of it outside the session "
                                      "jobs (they predate the PDB): re-open")
+                returning_job(jid, "PodDisruptionBudget of")
                 job = JobInfo(jid)
                 job.set_pdb(obj, default_queue)
                 job_add(job)
@@ -412,8 +464,12 @@ class Session:
                         e = ev()
                         e.kind, e.queue = _abi.EV_QUEUE_DELETE, q
                         for jid in [k for k, j in jidx.items() if job_of(j).queue == qi.uid]:
-                            jidx.pop(jid)  # its jobs leave ssn.Jobs (cache.go:584-588)
-                            outside.add(jid)
+                            job = job_of(jidx[jid])  # it leaves ssn.Jobs (cache.go:584-588); sc.Jobs keeps it
+                            away[jid] = SimpleNamespace(queue=qi.uid, pod_group=job.pod_group is not None,
+                                                        pdb=job.pdb is not None, pods=has_pods(jid))
+                            jidx.pop(jid)
+                            if away[jid].pods:
+                                outside.add(jid)
                     continue
                 q = qidx.get(qi.uid)
                 if q is not None and kind == "queue_add":  # sc.Queues[uid] = qi of a UID the cache holds: in place
@@ -429,6 +485,7 @@ class Session:
                     e.kind, e.queue = _abi.EV_QUEUE_UPDATE, q
                     queue_moved[q] = n_queues
                 else:  # (an update of a queue the cache does not hold deletes nothing and adds it)
+                    returning_queue(qi.uid)
                     e.kind = _abi.EV_QUEUE_ADD
                     keep.append(qi.uid.encode())
                     e.name = keep[-1]
@@ -447,6 +504,9 @@ class Session:
                 e.status = ti.status
                 if kind == "pod_update":
                     pod_node(e, ti.node_name)
+                else:
+                    dead_uids.add(ti.uid)
+                    live_delta[ti.job] = live_delta.get(ti.job, 0) - 1
                 objs[e.task] = ti
             elif kind == "pod_add":
                 if ti.job not in jidx:
@@ -465,12 +525,14 @@ class Session:
                 tidx[ti.uid] = n_objs
                 objs[n_objs] = ti
                 n_objs += 1
+                dead_uids.discard(ti.uid)
+                live_delta[ti.job] = live_delta.get(ti.job, 0) + 1
             else:
                 raise ValueError(f"unknown change {kind}")
         return SimpleNamespace(evs=evs, n_ev=n_ev, keep=keep, objs=objs, n_objs=n_objs, renamed=renamed, tidx=tidx,
                                new_nodes=new_nodes, new_jobs=new_jobs, new_queues=new_queues, pod_only=pod_only,
                                job_edits=job_edits, queue_weights=queue_weights, queue_moved=queue_moved,
-                               outside=outside)
+                               outside=outside, away=away, dead_uids=dead_uids, jidx=jidx, qidx=qidx)
 
     def _accept(self, plan, maps=None):
         """update's second half, once the library applied the batch: the
@@ -494,6 +556,8 @@ class Session:
         for q, weight in plan.queue_weights.items():
             self.queues[q].weight = weight
         self._outside_jobs().update(plan.outside)
+        self._away = plan.away
+        self._dead_uids().update(plan.dead_uids)
         structural = any(evs[k].kind in _abi.STRUCTURAL_EVENTS for k in range(n_ev))
         if structural or maps is not None:
             self._renumber(task_objs, new_nodes, new_jobs, new_queues, pod_only, maps=maps,
@@ -515,6 +579,24 @@ class Session:
             out |= {t.job for n in self.nodes for t in n.tasks.values() if t.uid not in mine}
             self._outside = out
         return self._outside
+
+    def _away_jobs(self):
+        """The cache's jobs outside ssn.Jobs: JobID -> its queue, whether it
+        holds a PodGroup, a PDB, pods. From the cache the session was opened on
+        (jobs whose queue was missing, jobs with neither PodGroup nor PDB), then
+        kept by the accepted batches (marshal / _accept)."""
+        if getattr(self, "_away", None) is None:
+            from types import SimpleNamespace
+            self._away = {jid: SimpleNamespace(queue=j.queue, pod_group=j.pod_group is not None,
+                                               pdb=j.pdb is not None, pods=bool(j.tasks))
+                          for jid, j in getattr(self.cache, "jobs", {}).items() if jid not in self.job_index}
+        return self._away
+
+    def _dead_uids(self):
+        """Pods deleted in place: they keep their index in the task list until the next renumbering."""
+        if getattr(self, "_dead", None) is None:
+            self._dead = set()
+        return self._dead
 
     def _renumber(self, task_objs, new_nodes, new_jobs, new_queues, pod_only, maps=None, queue_moved=None):
         """The wrapper's lists after a structural update, by the library's
@@ -549,6 +631,7 @@ class Session:
 
         rt, rn, rj, rq = (renum(k) for k in (_abi.RENUM_TASKS, _abi.RENUM_NODES, _abi.RENUM_JOBS, _abi.RENUM_QUEUES))
         flat.task_objs = remap(task_objs, rt)
+        self._dead_uids().clear()  # the library's renumbering dropped every deleted pod
         nodes = list(self.nodes) + [new_nodes[i] for i in sorted(new_nodes)]
         names = list(flat.node_names) + [new_nodes[i].name for i in sorted(new_nodes)]
         self.nodes = remap(nodes, rn)

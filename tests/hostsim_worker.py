@@ -364,10 +364,44 @@ def snapshots(cases_path, out_dir):
         json.dump(manifest, f)
 
 
+def revival(cases_path, out_path):
+    """Queue and job names that return to a resident session
+    (tests/revival_session.py, the bodies tests/test_revival_gpu.py runs on
+    the device): every comparison runs here and raises on the first
+    difference; the parent reads each case's record."""
+    assert os.environ.get("KBG_LIB_PATH") == LIB, "the parent sets KBG_LIB_PATH to the hostsim library"
+    import revival_session
+    with open(cases_path) as f:
+        cases = json.load(f)
+    res = {}
+    for c in cases:
+        t0 = time.time()
+        rec = {}
+        try:
+            if c["kind"] == "case":
+                want = revival_session.run_case(c["arg"], c.get("opts"))
+            elif c["kind"] == "seed":
+                want = revival_session.run_seed(c["arg"], c.get("opts"))
+            else:
+                want = revival_session.SPECIALS[c["arg"]]() or []
+            rec["refused"] = [v.round for v in want if v is not None]
+        except BaseException as e:  # (pytest.raises fails with an exception outside Exception)
+            if isinstance(e, (KeyboardInterrupt, SystemExit)):
+                raise
+            import traceback
+            rec = {"error": f"{type(e).__name__}: {e}\n{traceback.format_exc(limit=6)}"}
+        rec["s"] = round(time.time() - t0, 3)
+        res[c["id"]] = rec
+    with open(out_path, "w") as f:
+        json.dump(res, f)
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "kernels":
         kernels(sys.argv[2])
     elif sys.argv[1] == "parity":
         parity(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "revival":
+        revival(sys.argv[2], sys.argv[3])
     else:
         snapshots(sys.argv[2], sys.argv[3])
