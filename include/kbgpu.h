@@ -874,6 +874,48 @@ typedef struct kbg_fit_place {
  * call changes nothing: every later action returns what it would have. */
 kbg_status kbg_job_fit(kbg_session* s, const int32_t* jobs, int32_t n_jobs, int32_t limit, kbg_job_fit_row* out,
                        kbg_fit_place* places, int32_t places_cap, int32_t* n_places);
+
+/* Which Pending tasks a node would take now (additive within KBG_ABI_VERSION
+ * 13): kbg_task_reasons asked from the node's side, one row per named node.
+ * "This node sits idle while pods are pending: why does nobody land here?",
+ * "may I drain it, or can anything pending use it?". For a live node of
+ * ssn.Nodes every task that is Pending NOW (a live task with the session's
+ * status after the actions run so far; before the cycle's first action, the
+ * snapshot's; BestEffort tasks included) goes under exactly one cause: the one
+ * kbg_task_reasons gives this node in that task's row, the first that applies
+ * in the order of allocate.go:119-162 and backfill.go:50-64:
+ *   9 KBG_TWHY_PANIC             a nil Node under the predicates plugin (predicates.go:122-123)
+ *   0..5 KBG_WHY_*               the predicates plugin's first failing stage
+ *                                (predicates.go:125-198); none with the plugin off
+ *   6 KBG_TWHY_FITS_IDLE         Resreq.LessEqual(node.Idle), or a BestEffort task
+ *                                (backfill.go:47-60: no resource test)
+ *   7 KBG_TWHY_FITS_RELEASING    not Idle, but Resreq.LessEqual(node.Releasing)
+ *   8 KBG_TWHY_SHORT             neither
+ * idle_short counts, over the tasks of causes 7 and 8, the dimensions in which
+ * Idle.FitDelta(Resreq) is negative (resource_info.go:116-129, job_info.go:336-346).
+ * open_idle and open_releasing leave out the tasks whose queue is overused now
+ * (allocate.go:70-74: allocate would not reach them), the expression of
+ * kbg_task_why.queue_overused per task's queue. */
+typedef struct kbg_node_why {
+  int32_t valid;            /* 0: the node is not a live node of ssn.Nodes now; nothing below is set */
+  int32_t node;
+  int32_t pending;          /* Pending tasks now (BestEffort ones included) == sum(count) */
+  int32_t count[10];        /* tasks per cause, KBG_WHY_* 0..5 and KBG_TWHY_* 6..9 */
+  int32_t first_task[10];   /* lowest task index per cause, -1 when none */
+  int32_t idle_short[3];    /* over the tasks of causes 7 and 8: Idle.FitDelta(Resreq) negative in cpu, memory, GPU */
+  int32_t open_idle;        /* tasks of cause 6 whose queue is not overused now (allocate would reach them) */
+  int32_t open_releasing;   /* tasks of cause 7 whose queue is not overused now */
+  int32_t idle_best_effort; /* tasks of cause 6 that are BestEffort: backfill's, no resource test */
+  int32_t reserved[3];
+} kbg_node_why;
+/* out[i] describes nodes[i] (duplicates allowed; an index outside the
+ * session's nodes is KBG_E_INVALID); nodes == NULL describes every node
+ * (n_nodes must be the node count), as jobs == NULL in kbg_victim_reasons.
+ * Everything else as kbg_task_reasons: legal any time after open,
+ * KBG_E_INVALID on a session opened without kbg_options.reasons,
+ * KBG_E_UNSUPPORTED over a communicator or without a device. The call changes
+ * nothing: every later action returns what it would have. */
+kbg_status kbg_node_reasons(kbg_session* s, const int32_t* nodes, int32_t n_nodes, kbg_node_why* out);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

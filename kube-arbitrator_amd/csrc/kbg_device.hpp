@@ -601,4 +601,65 @@ inline const char* job_fit_refusal(const JobFitArgs& a) {
 hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
                           hipEvent_t stop = nullptr);
 
+// Which Pending tasks a node would take now (kbg_node_reasons): the table of
+// launch_task_why, (live node x shape) -> cause, reduced along the shape axis
+// with a weight per shape. A shape record is a TaskShape with the number of
+// Pending tasks of that key (`weight` >= 1), those of them whose queue is not
+// overused (0 <= weight_open <= weight) and the lowest task index of the key
+// (`first_task` >= 0). The causes, cap_check and LessEqual are launch_task_why's
+// to the letter; host ports, pod affinity and a nil Node are the host's.
+// `words` lists n_words words of the table, ascending and without repeats:
+// entry i names the table rows [64 * words[i], 64 * words[i] + 64), the global
+// nodes tab_lo + row. Only they are evaluated. `out` holds kNodeWhyFields
+// planes of `ostride` >= 64 * n_words words each, field-major, so the 64 lanes
+// of a wave store to 64 consecutive words of a plane: the slot of lane l of
+// entry i is 64 * i + l in every plane. The planes of a slot:
+//   kNwhyCount + k       tasks (sum of weight) under cause kNodeWhyCause[k]
+//   kNwhyFirst + k       lowest first_task under that cause, -1 none
+//   kNwhyShort + d       over causes 7 and 8: sum of weight where
+//                        Idle.FitDelta(req) is negative in cpu, memory, GPU
+//   kNwhyOpenIdle        sum of weight_open under kTwhyFitsIdle
+//   kNwhyOpenRel         sum of weight_open under kTwhyFitsReleasing
+//   kNwhyIdleBestEffort  sum of weight of BestEffort shapes under kTwhyFitsIdle
+// launch_node_why_init sets the slots [0, 64 * n_words) of every plane to their
+// empty value and nothing else; launch_node_why, after it on the same stream
+// and any number of times with further shapes, adds to the slots of live nodes
+// inside the table with integer atomics (add, and unsigned min with -1 the
+// empty value): the order of shape groups and launches is nothing. A slot of a
+// dead node, or of a row at or past tab_n, keeps its empty value; the words of
+// a plane from 64 * n_words on are never written. The sum of all weights must
+// not pass INT32_MAX (the session's task count bounds it). tab_lo is a multiple
+// of 64. The node table and the planes are read only.
+constexpr int kNodeWhyGroup = 32;  // shape records per workgroup
+constexpr int kNodeWhyWaves = 4;   // list entries per workgroup, one per wave
+constexpr int kNodeWhyCauses = 7;  // the device's causes
+constexpr int32_t kNodeWhyCause[kNodeWhyCauses] = {0, 1, 3, 4, kTwhyFitsIdle, kTwhyFitsReleasing, kTwhyShort};
+enum NodeWhy : int32_t {
+  kNwhyCount = 0,
+  kNwhyFirst = kNodeWhyCauses,
+  kNwhyShort = 2 * kNodeWhyCauses,
+  kNwhyOpenIdle = 2 * kNodeWhyCauses + 3,
+  kNwhyOpenRel = 2 * kNodeWhyCauses + 4,
+  kNwhyIdleBestEffort = 2 * kNodeWhyCauses + 5,
+  kNodeWhyFields = 2 * kNodeWhyCauses + 6
+};
+struct NodeWhyShape {
+  TaskShape sh;
+  int32_t weight, weight_open, first_task, pad;
+};
+struct NodeWhyArgs {
+  const double* nodes;  // the node table block (FirstFitArgs.nodes)
+  int32_t stride, W, tab_lo, tab_n;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const NodeWhyShape* shapes;                          // [n_shapes] staged in device memory
+  int32_t n_shapes, cap_check;
+  const int32_t* words;  // [n_words] staged in device memory
+  int32_t n_words;
+  int32_t ostride;
+  int32_t* out;  // [kNodeWhyFields][ostride]
+};
+hipError_t launch_node_why_init(int32_t* out, int32_t ostride, int32_t n_words, hipStream_t stream);
+hipError_t launch_node_why(const NodeWhyArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
+                           hipEvent_t stop = nullptr);
+
 }  // namespace kbg

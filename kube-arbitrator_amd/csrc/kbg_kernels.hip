@@ -1863,6 +1863,146 @@ hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t st
   return hipGetLastError();
 }
 
+// ------------------------------------------------- node reasons
+// kbg_node_reasons: the table of kbg_task_why_kernel reduced along the other
+// axis (kbg_device.hpp NodeWhy). Its geometry: a wave owns one 64-node word,
+// here an entry of the word list, loads its node records once, a lane per
+// node, and keeps them in registers with the word's wave-uniform live and
+// unsched bits; the workgroup's kNodeWhyWaves waves take consecutive entries
+// and its kNodeWhyGroup shape records sit in LDS, read as same-address
+// broadcasts. Per shape the same disjoint cause masks are built on the scalar
+// unit. The reduction runs per lane: a row of the answer is a node, so each
+// lane tests its own bit of each mask and adds the shape's weight to named
+// registers with selects (twenty of them; nothing is indexed, nothing goes to
+// scratch), and no lane ever talks to another. After its shapes a lane adds
+// its non-empty values to its slot of each plane: the wave's 64 slots of a
+// plane are 256 contiguous bytes, and integer add and unsigned min make the
+// order of shape groups and launches nothing.
+// Grid (entry blocks, shape groups): C3's 79 words x 302 shapes are 20 x 10
+// workgroups.
+__global__ __launch_bounds__(256) void kbg_node_why_init_kernel(int32_t* __restrict__ out, int32_t ostride,
+                                                                int32_t slots) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= slots) return;
+  const int f = blockIdx.y;
+  out[(size_t)f * ostride + i] = f >= kNwhyFirst && f < kNwhyShort ? -1 : 0;
+}
+
+__global__ __launch_bounds__(64 * kNodeWhyWaves) void kbg_node_why_kernel(NodeWhyArgs a) {
+  __shared__ NodeWhyShape s_shape[kNodeWhyGroup];
+  constexpr int kShapeWords = sizeof(NodeWhyShape) / 4;
+  const int lane = threadIdx.x & 63;
+  const int s0 = blockIdx.y * kNodeWhyGroup;
+  const int ns = min(kNodeWhyGroup, a.n_shapes - s0);
+  for (int i = threadIdx.x; i < ns * kShapeWords; i += 64 * kNodeWhyWaves)
+    reinterpret_cast<uint32_t*>(s_shape)[i] = reinterpret_cast<const uint32_t*>(a.shapes + s0)[i];
+  __syncthreads();
+  const int li = blockIdx.x * kNodeWhyWaves + (int)(threadIdx.x >> 6);  // the wave's entry of the list
+  if (li >= a.n_words) return;                                          // (wave-uniform, after the only barrier)
+  const int wl = a.words[li];                                           // its word of the table
+  if (wl < 0 || wl >= ((a.tab_n + 63) >> 6)) return;
+  const int w = (a.tab_lo >> 6) + wl;              // the global word
+  const int r = min(wl * 64 + lane, a.tab_n - 1);  // a legal row for the ragged word's lanes
+  const size_t L = (size_t)a.stride;
+  const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * L);
+  const double ic = a.nodes[r], im = a.nodes[L + r], ig = a.nodes[2 * L + r];
+  const double rc = a.nodes[3 * L + r], rm = a.nodes[4 * L + r], rg = a.nodes[5 * L + r];
+  uint64_t valid = a.live[w];
+  if (wl * 64 + 64 > a.tab_n) valid &= (1ull << (a.tab_n - wl * 64)) - 1ull;  // bits past the table's last node
+  const uint64_t capped = a.cap_check ? __ballot(ni[r] >= ni[L + r]) : 0ull;   // predicates.go:125-127
+  const uint64_t uns = a.cap_check ? a.unsched[w] : 0ull;
+  const uint64_t me = 1ull << lane;
+  uint32_t n0 = 0, n1 = 0, n3 = 0, n4 = 0, n6 = 0, n7 = 0, n8 = 0;
+  uint32_t f0 = ~0u, f1 = ~0u, f3 = ~0u, f4 = ~0u, f6 = ~0u, f7 = ~0u, f8 = ~0u;
+  uint32_t hc = 0, hm = 0, hg = 0, oi = 0, orl = 0, be = 0;
+  for (int s = 0; s < ns; ++s) {
+    const NodeWhyShape& rec = s_shape[s];
+    const TaskShape& sh = rec.sh;
+    const uint64_t so = a.cap_check ? a.sel_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+    const uint64_t to = a.cap_check ? a.taint_ok[(size_t)sh.cls * a.W + w] : ~0ull;
+    const double q0 = sh.req[0], q1 = sh.req[1], q2 = sh.req[2];
+    const uint64_t c0 = valid & capped;
+    uint64_t rest = valid & ~capped;
+    const uint64_t c1 = rest & ~so;  // :129-141
+    rest &= so;
+    const uint64_t c3 = rest & uns;  // :157-169
+    rest &= ~uns;
+    const uint64_t c4 = rest & ~to;  // :171-183
+    rest &= to;
+    const bool beff = (sh.flags & kTaskShapeBestEffort) != 0;
+    const uint64_t fi = beff ? ~0ull : fit_mask<false>(ic, im, ig, q0, q1, q2);
+    const uint64_t fr = fit_mask<false>(rc, rm, rg, q0, q1, q2);
+    const uint64_t c6 = rest & fi;
+    rest &= ~fi;  // FitDelta's nodes (allocate.go:127-133): causes 7 and 8
+    const uint64_t c7 = rest & fr, c8 = rest & ~fr;
+    const uint64_t bc = rest & __ballot((q0 > 0 ? ic - (q0 + kMinMilliCPU) : ic) < 0);
+    const uint64_t bm = rest & __ballot((q1 > 0 ? im - (q1 + kMinMemory) : im) < 0);
+    const uint64_t bg = rest & __ballot((q2 > 0 ? ig - (q2 + kMinMilliGPU) : ig) < 0);
+    const uint32_t wt = (uint32_t)rec.weight, wo = (uint32_t)rec.weight_open, ft = (uint32_t)rec.first_task;
+    const bool i0 = c0 & me, i1 = c1 & me, i3 = c3 & me, i4 = c4 & me, i6 = c6 & me, i7 = c7 & me, i8 = c8 & me;
+    n0 += i0 ? wt : 0u;
+    n1 += i1 ? wt : 0u;
+    n3 += i3 ? wt : 0u;
+    n4 += i4 ? wt : 0u;
+    n6 += i6 ? wt : 0u;
+    n7 += i7 ? wt : 0u;
+    n8 += i8 ? wt : 0u;
+    f0 = i0 ? min(f0, ft) : f0;
+    f1 = i1 ? min(f1, ft) : f1;
+    f3 = i3 ? min(f3, ft) : f3;
+    f4 = i4 ? min(f4, ft) : f4;
+    f6 = i6 ? min(f6, ft) : f6;
+    f7 = i7 ? min(f7, ft) : f7;
+    f8 = i8 ? min(f8, ft) : f8;
+    hc += (bc & me) ? wt : 0u;
+    hm += (bm & me) ? wt : 0u;
+    hg += (bg & me) ? wt : 0u;
+    oi += i6 ? wo : 0u;
+    orl += i7 ? wo : 0u;
+    be += (i6 && beff) ? wt : 0u;
+  }
+  if (!(valid & me)) return;  // a dead node, a lane past the table's last node: nothing is written
+  uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + (size_t)li * 64 + lane;
+  const size_t P = (size_t)a.ostride;
+  if (n0) atomicAdd(o + (kNwhyCount + 0) * P, n0);
+  if (n1) atomicAdd(o + (kNwhyCount + 1) * P, n1);
+  if (n3) atomicAdd(o + (kNwhyCount + 2) * P, n3);
+  if (n4) atomicAdd(o + (kNwhyCount + 3) * P, n4);
+  if (n6) atomicAdd(o + (kNwhyCount + 4) * P, n6);
+  if (n7) atomicAdd(o + (kNwhyCount + 5) * P, n7);
+  if (n8) atomicAdd(o + (kNwhyCount + 6) * P, n8);
+  if (f0 != ~0u) atomicMin(o + (kNwhyFirst + 0) * P, f0);
+  if (f1 != ~0u) atomicMin(o + (kNwhyFirst + 1) * P, f1);
+  if (f3 != ~0u) atomicMin(o + (kNwhyFirst + 2) * P, f3);
+  if (f4 != ~0u) atomicMin(o + (kNwhyFirst + 3) * P, f4);
+  if (f6 != ~0u) atomicMin(o + (kNwhyFirst + 4) * P, f6);
+  if (f7 != ~0u) atomicMin(o + (kNwhyFirst + 5) * P, f7);
+  if (f8 != ~0u) atomicMin(o + (kNwhyFirst + 6) * P, f8);
+  if (hc) atomicAdd(o + (kNwhyShort + 0) * P, hc);
+  if (hm) atomicAdd(o + (kNwhyShort + 1) * P, hm);
+  if (hg) atomicAdd(o + (kNwhyShort + 2) * P, hg);
+  if (oi) atomicAdd(o + kNwhyOpenIdle * P, oi);
+  if (orl) atomicAdd(o + kNwhyOpenRel * P, orl);
+  if (be) atomicAdd(o + kNwhyIdleBestEffort * P, be);
+}
+
+hipError_t launch_node_why_init(int32_t* out, int32_t ostride, int32_t n_words, hipStream_t stream) {
+  if (n_words <= 0) return hipSuccess;
+  if ((int64_t)n_words * 64 > ostride) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kbg_node_why_init_kernel, dim3((n_words * 64 + 255) / 256, kNodeWhyFields), dim3(256), 0, stream,
+                     out, ostride, n_words * 64);
+  return hipGetLastError();
+}
+
+hipError_t launch_node_why(const NodeWhyArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if ((int64_t)a.n_words * 64 > a.ostride) return hipErrorInvalidValue;
+  if (a.n_shapes <= 0 || a.tab_n <= 0 || a.n_words <= 0) return hipSuccess;
+  hipExtLaunchKernelGGL(kbg_node_why_kernel,
+                        dim3((a.n_words + kNodeWhyWaves - 1) / kNodeWhyWaves, (a.n_shapes + kNodeWhyGroup - 1) / kNodeWhyGroup),
+                        dim3(64 * kNodeWhyWaves), 0, stream, start, stop, 0, a);
+  return hipGetLastError();
+}
+
 __device__ __forceinline__ void apply_node_delta(const NodeSoA& nd, const NodeDelta& x) {
   nd.idle_cpu[x.node] = x.idle[0];
   nd.idle_mem[x.node] = x.idle[1];

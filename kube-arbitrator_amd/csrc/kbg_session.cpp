@@ -783,6 +783,9 @@ void free_device(Session& S) {
   S.d_fit_steps = nullptr;
   S.d_fit_off = S.d_fit_out = nullptr;
   S.fit_shape_cap = S.fit_step_cap = S.fit_job_cap = 0;
+  S.d_nwhy_shapes = nullptr;  // (d_allocs too)
+  S.d_nwhy_words = S.d_nwhy_out = nullptr;
+  S.nwhy_shape_cap = S.nwhy_word_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1104,6 +1107,8 @@ kbg_status device_scan(Session& S, kbg::Stage& sg, int32_t G, int32_t base) {
 #include "kbg_headroom.ipp"  // kbg_task_headroom: how many copies of a Pending task fit now
 
 #include "kbg_job_fit.ipp"  // kbg_job_fit: where a job's Pending tasks would land now
+
+#include "kbg_node_why.ipp"  // kbg_node_reasons: which Pending tasks a node would take now
 
 #include "kbg_update.ipp"  // resident session updates (kbg_session_update)
 
@@ -1484,6 +1489,18 @@ kbg_status kbg_job_fit(kbg_session* s, const int32_t* jobs, int32_t n_jobs, int3
   if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
   try {
     return job_fit(s->s, jobs, n_jobs, limit, out, places, places_cap, n_places);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
+}
+
+kbg_status kbg_node_reasons(kbg_session* s, const int32_t* nodes, int32_t n_nodes, kbg_node_why* out) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return node_reasons(s->s, nodes, n_nodes, out);
   } catch (const std::bad_alloc&) {
     return fail(KBG_E_NOMEM, "host allocation failed");
   } catch (const std::exception& e) {

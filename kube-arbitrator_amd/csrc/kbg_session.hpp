@@ -600,6 +600,10 @@ struct Session {
   kbg::JobFitStep* d_fit_steps = nullptr;
   int32_t *d_fit_off = nullptr, *d_fit_out = nullptr;
   size_t fit_shape_cap = 0, fit_step_cap = 0, fit_job_cap = 0;
+  // kbg_node_reasons: the staged shape records, the word list and the result planes (HBM, grown on demand)
+  kbg::NodeWhyShape* d_nwhy_shapes = nullptr;
+  int32_t *d_nwhy_words = nullptr, *d_nwhy_out = nullptr;
+  size_t nwhy_shape_cap = 0, nwhy_word_cap = 0;       // shape records / words (64 slots of every plane each)
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while

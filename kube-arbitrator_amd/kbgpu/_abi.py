@@ -212,6 +212,12 @@ class kbg_fit_place(ctypes.Structure):
     _fields_ = [("task", i32), ("node", i32), ("kind", i32), ("reserved", i32)]
 
 
+class kbg_node_why(ctypes.Structure):
+    _fields_ = [("valid", i32), ("node", i32), ("pending", i32), ("count", i32 * 10), ("first_task", i32 * 10),
+                ("idle_short", i32 * 3), ("open_idle", i32), ("open_releasing", i32), ("idle_best_effort", i32),
+                ("reserved", i32 * 3)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -306,6 +312,7 @@ SIGNATURES = {
     "kbg_task_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_task_why)]),
     "kbg_task_headroom": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_task_room)]),
     "kbg_job_fit": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_job_fit), P(kbg_fit_place), i32, P(i32)]),
+    "kbg_node_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_node_why)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -141,6 +141,31 @@ def job_fit_message(row):
             f"{row['nodes_used']} nodes): {end}{tail}")
 
 
+def node_message(row):
+    """One line for a node (a Session.node_reasons row): how many of the
+    pending pods it would take now and once resources are released, then the
+    pods it turns away by predicate stage and FitError's resource parts over
+    the pods that pass every stage but find too little Idle here, each group
+    sorted as pending_message sorts its own."""
+    if not row["valid"]:
+        return "not a live node"
+    count, total = row["count"], row["pending"]
+    if total == 0:
+        return "no pods are pending"
+    idle, rel = count[_abi.TWHY_FITS_IDLE], count[_abi.TWHY_FITS_RELEASING]
+    head = f"takes {idle} of {total} pending pods now"
+    if idle:
+        head += f" ({row['open_idle']} in queues that are not overused, {row['idle_best_effort']} best-effort)"
+    if rel:
+        head += f", {rel} more once resources are released"
+    parts = sorted(f"{n} {text}" for n, text in zip(count, STAGE_TEXTS) if n > 0)
+    if count[_abi.TWHY_PANIC]:
+        parts.append(f"{count[_abi.TWHY_PANIC]} no Node object")
+    if count[_abi.TWHY_SHORT]:
+        parts += sorted(f"{v} insufficient {k}" for k, v in zip(("cpu", "memory", "GPU"), row["idle_short"]) if v > 0)
+    return head + (f"; turned away: {', '.join(parts)}" if parts else "")
+
+
 def reasons_row(st):
     """A kbg_job_reasons as the output rows carry it."""
     return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),

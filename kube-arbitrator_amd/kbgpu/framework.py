@@ -738,6 +738,22 @@ class Session:
             rows.append(row)
         return rows
 
+    def node_reasons(self, nodes=None):
+        """One dict per node (the indices `nodes`, duplicates allowed, or every
+        node): the tasks that are Pending now by the cause kbg_task_reasons
+        gives this node in their rows, with the lowest task index per cause
+        (kbg_node_why). Legal any time after open on sessions opened with
+        reasons=True; changes nothing."""
+        if nodes is None:
+            n, arr = len(self.flat.node_names), None
+        else:
+            n, arr = len(nodes), (ctypes.c_int32 * max(len(nodes), 1))(*nodes)
+        out = (_abi.kbg_node_why * max(n, 1))()
+        _abi.check(_abi.lib().kbg_node_reasons(self.handle, arr, n, out))
+        return [{"valid": bool(r.valid), "node": r.node, "pending": r.pending, "count": list(r.count),
+                 "first_task": list(r.first_task), "idle_short": list(r.idle_short), "open_idle": r.open_idle,
+                 "open_releasing": r.open_releasing, "idle_best_effort": r.idle_best_effort} for r in out[:n]]
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))

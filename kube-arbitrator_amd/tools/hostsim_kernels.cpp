@@ -12,7 +12,8 @@
 // (tests/victim_why_ref.py), tests/test_hostsim_task_why.py for the
 // pending-task reasons (tests/task_why_ref.py), tests/test_hostsim_headroom.py
 // for the pending-task headroom (tests/headroom_ref.py),
-// tests/test_hostsim_job_fit.py for the job fit walk (tests/job_fit_ref.py).
+// tests/test_hostsim_job_fit.py for the job fit walk (tests/job_fit_ref.py),
+// tests/test_hostsim_node_why.py for the node reasons (tests/node_why_ref.py).
 //
 // The victim launchers count their launches (kbg_hostsim_launch_counts, an
 // export of libkbg_hostsim.so alone): tests/test_hostsim_parity.py asserts
@@ -627,6 +628,50 @@ void task_why_run(const TaskWhyArgs& a) {
   }
 }
 
+// ---- node reasons (kbg_device.hpp NodeWhy): the slots [0, 64 * n_words) of
+// every plane get their empty value; then each listed word's live rows inside
+// the table take every shape record under task_why_cause's cause.
+void node_why_init_run(int32_t* out, int32_t ostride, int32_t n_words) {
+  for (int f = 0; f < kNodeWhyFields; ++f)
+    std::fill_n(out + (size_t)f * ostride, (size_t)n_words * 64, f >= kNwhyFirst && f < kNwhyShort ? -1 : 0);
+}
+
+void node_why_run(const NodeWhyArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  TaskWhyArgs ta{};
+  ta.W = a.W;
+  ta.tab_lo = a.tab_lo;
+  ta.sel_ok = a.sel_ok;
+  ta.taint_ok = a.taint_ok;
+  ta.unsched = a.unsched;
+  ta.cap_check = a.cap_check;
+  const size_t P = (size_t)a.ostride;
+  for (int32_t i = 0; i < a.n_words; ++i)
+    for (int32_t l = 0; l < 64; ++l) {
+      const int32_t row = a.words[i] * 64 + l, n = a.tab_lo + row;
+      if (row >= a.tab_n || !((a.live[n >> 6] >> (n & 63)) & 1ull)) continue;
+      int32_t* o = a.out + (size_t)i * 64 + l;
+      for (int32_t s = 0; s < a.n_shapes; ++s) {
+        const NodeWhyShape& r = a.shapes[s];
+        int32_t idle_short = 0;
+        const int32_t c = task_why_cause(ta, t, r.sh, row, &idle_short);
+        int k = 0;
+        while (kNodeWhyCause[k] != c) ++k;
+        o[(kNwhyCount + k) * P] += r.weight;
+        int32_t& first = o[(kNwhyFirst + k) * P];
+        if (first < 0 || r.first_task < first) first = r.first_task;
+        for (int d = 0; d < 3; ++d)
+          if ((idle_short >> d) & 1) o[(kNwhyShort + d) * P] += r.weight;
+        if (c == kTwhyFitsIdle) {
+          o[kNwhyOpenIdle * P] += r.weight_open;
+          if (r.sh.flags & kTaskShapeBestEffort) o[kNwhyIdleBestEffort * P] += r.weight;
+        } else if (c == kTwhyFitsReleasing) {
+          o[kNwhyOpenRel * P] += r.weight_open;
+        }
+      }
+    }
+}
+
 // ---- pending-task headroom (kbg_device.hpp TaskRoom): the copies of shape sh
 // table row `row` takes one after the other, {from Idle, from Releasing}, with
 // *pass whether the node is past the stages and *cut whether `limit` ended the
@@ -778,13 +823,14 @@ enum Count : int {
   kCountTaskWhy,
   kCountTaskHeadroom,
   kCountStageMask,
+  kCountNodeWhy,  // (ahead of the last two: tests/test_hostsim_job_fit.py names the list's end)
   kCountVictimWhy,
   kCountJobFit,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,victim_why,job_fit";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,node_why,victim_why,job_fit";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -983,6 +1029,19 @@ hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t st
   if (a.n_jobs <= 0 || a.tab_n <= 0) return hipSuccess;
   g_count[kCountJobFit]++;
   return launch(stream, start, stop, [a] { job_fit_run(a); });
+}
+
+hipError_t launch_node_why_init(int32_t* out, int32_t ostride, int32_t n_words, hipStream_t stream) {
+  if (n_words <= 0) return hipSuccess;
+  if ((int64_t)n_words * 64 > ostride) return hipErrorInvalidValue;
+  return launch(stream, nullptr, nullptr, [out, ostride, n_words] { node_why_init_run(out, ostride, n_words); });
+}
+
+hipError_t launch_node_why(const NodeWhyArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if ((int64_t)a.n_words * 64 > a.ostride) return hipErrorInvalidValue;
+  if (a.n_shapes <= 0 || a.tab_n <= 0 || a.n_words <= 0) return hipSuccess;
+  g_count[kCountNodeWhy]++;
+  return launch(stream, start, stop, [a] { node_why_run(a); });
 }
 
 }  // namespace kbg

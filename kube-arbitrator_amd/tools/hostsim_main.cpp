@@ -6,6 +6,7 @@
 //   hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions a,b,...]
 //                [--batch-tasks N] [--candidates N] [--full-scan]
 //                [--general-scan] [--repeat N] [--victim-reasons] [--job-fit]
+//                [--node-why]
 //
 // Each repeat opens a session, runs the actions (reclaim, allocate, backfill,
 // preempt, in the order given), resets the session, runs them again and
@@ -21,6 +22,11 @@
 // kbg_job_fit for every job before the first action and after each one (once
 // per action prefix), at limit 512 with the places and at limit 2 without. The
 // rows do not go to OUT either; a summary goes to stderr.
+// --node-why opens the session with kbg_options.reasons too and calls
+// kbg_node_reasons before the first action and after each one, for every node
+// and for a named subset (the last node, the first, the last again and every
+// 70th: duplicates, out of order, one word or several). The rows do not go to
+// OUT either; a summary goes to stderr.
 // Exit status 0 unless the arguments or the files are unusable.
 #include <cstdio>
 #include <cstdlib>
@@ -100,11 +106,40 @@ void job_fit(kbg_session* s, const std::string& after, int32_t n_jobs) {
           after.c_str(), (long long)valid, (long long)idle, (long long)rel, (long long)nowhere, (long long)ready);
 }
 
+// kbg_node_reasons of every node and of a named subset; what it found, to stderr.
+void node_why(kbg_session* s, const std::string& after, int32_t n_nodes) {
+  std::vector<kbg_node_why> all((size_t)n_nodes + 1);
+  std::vector<int32_t> pick;
+  if (n_nodes > 0) pick = {n_nodes - 1, 0, n_nodes - 1};
+  for (int32_t i = 70; i < n_nodes; i += 70) pick.push_back(i);
+  std::vector<kbg_node_why> some(pick.size() + 1);
+  kbg_status st = kbg_node_reasons(s, nullptr, n_nodes, all.data());
+  if (st == KBG_OK) st = kbg_node_reasons(s, pick.data(), (int32_t)pick.size(), some.data());
+  if (st != KBG_OK) {
+    fprintf(stderr, "hostsim_main: node why after %s: status %d: %s\n", after.c_str(), (int)st, kbg_last_error());
+    return;
+  }
+  int64_t valid = 0, pending = 0, count[KBG_TWHY_COUNT] = {}, open = 0, differ = 0;
+  for (int32_t i = 0; i < n_nodes; ++i) {
+    if (!all[i].valid) continue;
+    ++valid;
+    pending = all[i].pending;
+    for (int c = 0; c < KBG_TWHY_COUNT; ++c) count[c] += all[i].count[c];
+    open += all[i].open_idle + all[i].open_releasing;
+  }
+  for (size_t k = 0; k < pick.size(); ++k) differ += memcmp(&some[k], &all[pick[k]], sizeof(kbg_node_why)) != 0;
+  fprintf(stderr, "hostsim_main: node why after %s: %lld live nodes, %lld Pending tasks; pairs per cause", after.c_str(),
+          (long long)valid, (long long)pending);
+  for (int c = 0; c < KBG_TWHY_COUNT; ++c) fprintf(stderr, " %lld", (long long)count[c]);
+  fprintf(stderr, "; %lld open; %lld of %zu named rows differ\n", (long long)open, (long long)differ, pick.size());
+}
+
 void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
-                 std::vector<char>& out, int32_t why_jobs = -1, int32_t fit_jobs = -1) {
+                 std::vector<char>& out, int32_t why_jobs = -1, int32_t fit_jobs = -1, bool nwhy = false) {
   std::vector<kbg_decision> dec((size_t)n_tasks + 1);
   int32_t n = 0;
   if (fit_jobs >= 0) job_fit(s, "open", fit_jobs);
+  if (nwhy) node_why(s, "open", n_nodes);
   for (const std::string& a : actions) {
     const kbg_status st = run_action(s, a, dec.data(), (int32_t)dec.size(), &n);
     put_i32(out, (int32_t)st);
@@ -115,6 +150,7 @@ void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_
     }
     if (why_jobs >= 0 && (a == "reclaim" || a == "preempt")) victim_reasons(s, a, why_jobs);
     if (fit_jobs >= 0) job_fit(s, a, fit_jobs);
+    if (nwhy) node_why(s, a, n_nodes);
   }
   // the decision log (Allocate and Pipeline decisions of every action) and the action behind each
   put_i32(out, n);
@@ -143,7 +179,7 @@ int usage() {
   fprintf(stderr,
           "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions reclaim,allocate,backfill,preempt]\n"
           "                    [--batch-tasks N] [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n"
-          "                    [--victim-reasons] [--job-fit]\n"
+          "                    [--victim-reasons] [--job-fit] [--node-why]\n"
           "  --actions: any of reclaim, allocate, backfill, preempt, run in the order given (default allocate)\n");
   return 2;
 }
@@ -156,7 +192,7 @@ int main(int argc, char** argv) {
   memset(&opts, 0, sizeof opts);
   std::vector<std::string> actions{"allocate"};
   int repeat = 1;
-  bool why = false, fit = false;
+  bool why = false, fit = false, nwhy = false;
   for (int i = 3; i < argc; ++i) {
     const std::string a = argv[i];
     const bool more = i + 1 < argc;
@@ -189,6 +225,9 @@ int main(int argc, char** argv) {
     } else if (a == "--job-fit") {
       fit = true;
       opts.reasons = 1;
+    } else if (a == "--node-why") {
+      nwhy = true;
+      opts.reasons = 1;
     } else if (a == "--repeat" && more) {
       repeat = atoi(argv[++i]);
     } else {
@@ -210,10 +249,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "hostsim_main: open: status %d: %s\n", (int)st, kbg_last_error());
       continue;
     }
-    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1);
+    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy);
     const kbg_status rs = kbg_session_reset(s);
     put_i32(out, (int32_t)rs);
-    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1);
+    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy);
     kbg_session_close(s);
   }
   kbg_snapshot_blob_free(blob);

@@ -10,7 +10,8 @@
 // the pending-task reasons (tests/task_why_ref.py),
 // tests/test_headroom_kernels_gpu.py for the pending-task headroom
 // (tests/headroom_ref.py), tests/test_job_fit_kernels_gpu.py for the job fit
-// walk (tests/job_fit_ref.py).
+// walk (tests/job_fit_ref.py), tests/test_node_why_kernels_gpu.py for the node
+// reasons (tests/node_why_ref.py).
 //
 // Output buffers are filled with kProbeSentinel bytes before the launch and
 // are followed by a guard region of kProbeGuardBytes of the same pattern; the
@@ -999,6 +1000,103 @@ extern "C" int32_t kbg_tool_probe_job_fit(const kbg_probe_job_fit* p, void* node
   (void)hipEventDestroy(ev[1]);
   PROBE_TRY(e);
   t_job_fit_ms = ms;
+  PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// kbg_node_why_init_kernel, then kbg_node_why_kernel, as kbg_node_reasons runs
+// them for n_shapes shape records over the listed words at once.
+thread_local double t_node_why_ms = 0;  // the HIP-event time of the last kbg_node_why_kernel launch
+extern "C" double kbg_tool_probe_node_why_ms() { return t_node_why_ms; }
+
+struct kbg_probe_node_why {
+  int32_t n_nodes, W, tab_lo, tab_n;  // the table holds the global nodes [tab_lo, tab_lo + tab_n)
+  int32_t stride;                     // rows of the node table block (row = node - tab_lo)
+  int32_t classes;                    // rows of the per-class stage planes
+  int32_t n_shapes, cap_check;
+  int32_t n_words;  // entries of the word list
+  int32_t ostride;  // words of an output plane, >= 64 * n_words
+};
+
+// The arrays of kbg_tool_probe_task_why with kbg::NodeWhyShape records, and
+// the word list (words of the table, ascending, no repeats). out:
+// kNodeWhyFields * ostride words + guard, device memory filled with the
+// sentinel before the launches. Refused (-2) is what kbg_node_reasons never
+// launches: a weight < 1, weight_open outside [0, weight], a negative
+// first_task, weights summing past INT32_MAX, a word list that is unsorted,
+// repeats a word or leaves the table, planes too short for the list. The node
+// block is copied back so the caller sees it untouched.
+extern "C" int32_t kbg_tool_probe_node_why(const kbg_probe_node_why* p, void* nodes, const uint64_t* planes,
+                                           const kbg::NodeWhyShape* shapes, const int32_t* words, void* out) {
+  t_error.clear();
+  if (!p || !nodes || !planes || !shapes || !words || !out) return reject("null argument");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->tab_lo < 0 || (p->tab_lo & 63)) return reject("tab_lo not a multiple of 64");
+  if (p->tab_n < 1 || (int64_t)p->tab_lo + p->tab_n > p->n_nodes) return reject("node range outside n_nodes");
+  if (p->stride < 1 || p->tab_n > p->stride) return reject("node range outside the table block");
+  if (p->classes < 1) return reject("no class");
+  if (p->n_shapes < 1 || p->n_shapes > (1 << 20)) return reject("n_shapes outside 1..2^20");
+  int64_t sum = 0;
+  for (int32_t i = 0; i < p->n_shapes; ++i) {
+    const kbg::NodeWhyShape& r = shapes[i];
+    if (r.sh.cls < 0 || r.sh.cls >= p->classes) return reject("shape: cls outside the planes");
+    if (r.weight < 1) return reject("shape: weight below 1");
+    if (r.weight_open < 0 || r.weight_open > r.weight) return reject("shape: weight_open outside 0..weight");
+    if (r.first_task < 0) return reject("shape: negative first_task");
+    if ((sum += r.weight) > INT32_MAX) return reject("the weights sum past INT32_MAX");
+  }
+  const int32_t tab_words = (p->tab_n + 63) >> 6;
+  if (p->n_words < 1 || p->n_words > tab_words) return reject("word list: n_words outside 1..the table's words");
+  for (int32_t i = 0; i < p->n_words; ++i) {
+    if (words[i] < 0 || words[i] >= tab_words) return reject("word list: a word outside the table");
+    if (i && words[i] <= words[i - 1]) return reject("word list: not ascending or a word twice");
+  }
+  if (p->ostride < p->n_words * 64) return reject("ostride below 64 * n_words");
+  if ((int64_t)p->ostride * kbg::kNodeWhyFields * 4 > (1ll << 30)) return reject("ostride too large");
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)p->stride;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  uint64_t* d_planes = nullptr;
+  PROBE_TRY(dev_copy(sc, &d_planes, planes, kbg::kbg_stage_words(p->classes, p->W)));
+  const kbg::StagePlanes sp = kbg::kbg_stage_planes(d_planes, p->classes, p->W);
+  kbg::NodeWhyArgs a{};
+  a.nodes = d;
+  a.stride = p->stride;
+  a.W = p->W;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  a.sel_ok = sp.sel_ok;
+  a.taint_ok = sp.taint_ok;
+  a.unsched = sp.unsched;
+  a.live = sp.live;
+  PROBE_TRY(dev_copy(sc, (kbg::NodeWhyShape**)&a.shapes, shapes, (size_t)p->n_shapes));
+  a.n_shapes = p->n_shapes;
+  a.cap_check = p->cap_check ? 1 : 0;
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.words, words, (size_t)p->n_words));
+  a.n_words = p->n_words;
+  a.ostride = p->ostride;
+  const size_t out_bytes = (size_t)p->ostride * kbg::kNodeWhyFields * 4 + kProbeGuardBytes;
+  PROBE_TRY(dev_copy(sc, (char**)&a.out, (const char*)nullptr, out_bytes, kProbeSentinel));
+
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  PROBE_TRY(hipEventCreate(&ev[0]));
+  if (const hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
+    (void)hipEventDestroy(ev[0]);
+    return hip_fail(e, "hipEventCreate");
+  }
+  hipError_t e = kbg::launch_node_why_init(a.out, a.ostride, a.n_words, sc.stream);
+  if (e == hipSuccess) e = kbg::launch_node_why(a, sc.stream, ev[0], ev[1]);
+  if (e == hipSuccess) e = hipStreamSynchronize(sc.stream);
+  float ms = 0;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  PROBE_TRY(e);
+  t_node_why_ms = ms;
   PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
   PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
   return 0;
