@@ -916,6 +916,93 @@ typedef struct kbg_node_why {
  * KBG_E_UNSUPPORTED over a communicator or without a device. The call changes
  * nothing: every later action returns what it would have. */
 kbg_status kbg_node_reasons(kbg_session* s, const int32_t* nodes, int32_t n_nodes, kbg_node_why* out);
+
+/* Where a node's running pods would land if it left (additive within
+ * KBG_ABI_VERSION 13): the other half of "may I drain it", what an operator
+ * or an autoscaler's scale-down asks before it removes a node. "18 of 20 pods
+ * find room (2 on releasing resources, 5 nodes); 2 do not, first task 7713;
+ * breaks 1 gang."
+ * Each named node is drained alone, from the session as it is NOW (before the
+ * cycle's first action: the snapshot); rows do not see each other's
+ * hypothetical placements.
+ * The moved tasks are the session tasks of the node in NodeInfo.Tasks order,
+ * the order preempt and reclaim take victims in, that are live and whose
+ * status now satisfies AllocatedStatus (Allocated, Binding, Bound, Running;
+ * api/helpers.go:63-70); the first `limit` of them are walked (1..
+ * KBG_FIT_MAX_LIMIT). Releasing and Pipelined session tasks, session tasks in
+ * any other status and the pods outside the session jobs (the node's key_len -
+ * task_len) are not walked: other_pods counts them. What the cycle's own
+ * actions put on the node so far follows the tasks it held at open, in the
+ * order of the decision log: an Allocate joins the moved tasks, a Pipeline the
+ * other pods (session.go:205-293: ssn.Allocate and ssn.Pipeline end in
+ * node.AddTask, node_info.go:101-129, so NodeInfo.Tasks holds them; Allocated
+ * and Binding, which AllocatedStatus names, arise in no other way within a
+ * session).
+ * The view is kbg_job_fit's: Idle, Releasing, pod count, used host ports and
+ * held pod keys of every live node, private to the row. The drained node and
+ * every node of `cordon` take nothing, with the predicates plugin off as
+ * well. `cordon` is common to the whole call ("...given that these also go
+ * away"): NULL with n_cordon == 0 is none, an index outside the session's
+ * nodes is KBG_E_INVALID, a dead node in it is ignored, duplicates are
+ * allowed. Nothing is given back to the drained node's own Idle.
+ * A task with a request is walked by kbg_job_fit's rule to the letter
+ * (allocate.go:119-162, node_info.go:101-129, session.go:205-293): the nodes
+ * in index order, the first that passes the predicate stages against the view
+ * and has Resreq.LessEqual(Idle) is an Allocate; otherwise, on that same node,
+ * LessEqual(Releasing) is a Pipeline; the subtraction is plain fp64, the
+ * node's pod count grows by one and the pod's host ports join the node's; a
+ * placement on a node whose view already holds the PodKey is reported and
+ * leaves the view unchanged (node_info.go:101-106); a nil-Node node takes
+ * nothing; a task no node takes has node -1 and the walk goes on
+ * (allocate.go:170).
+ * A BestEffort task (Resreq.IsEmpty()) follows backfill's rule
+ * (backfill.go:47-64): the first node that passes the stages, no resource
+ * test, an Allocate; the pod count grows by one, the host ports join, and
+ * AddTask's Idle.Sub takes the request, every dimension of which is below its
+ * min (node_info.go:108-118).
+ * Host ports: a moved pod's own port entries are held against the node's used
+ * ports of now and against the ports of the pods the row placed there before
+ * it (predicates.go:143-155, host_ports.go); the moved pods still count where
+ * they are.
+ * Pod affinity: in a session with required pod (anti)affinity under the
+ * predicates plugin the verdict of now applies to every step and affinity_now
+ * is 1 in every valid row (kbg_task_headroom's and kbg_job_fit's rule;
+ * predicates.go:185-198): each moved pod's terms, and the anti terms of the
+ * pods that are allocated now, are held against the AllocatedStatus pods as
+ * they are, the moved pods still counted where they are; what the walked pods
+ * would do to each other's (anti)affinity is not modelled.
+ * Queues are not consulted; nothing is enqueued. */
+typedef struct kbg_node_drain {
+  int32_t valid;            /* 0: the node is not a live node of ssn.Nodes now; nothing below is set */
+  int32_t node;
+  int32_t tasks;            /* the movable tasks now (0: a live node with nothing to move) */
+  int32_t walked;           /* min(tasks, limit) */
+  int32_t placed_idle;      /* walked tasks that would be Allocate decisions */
+  int32_t placed_releasing; /* ... Pipeline decisions */
+  int32_t unplaced;         /* walked tasks no node takes: placed_idle + placed_releasing + unplaced == walked */
+  int32_t first_unplaced;   /* the first of them (task index), -1 when none */
+  int32_t nodes_used;       /* distinct nodes taking at least one */
+  int32_t other_pods;       /* pods of the node that are not walked at any limit: see above */
+  int32_t jobs_moved;       /* distinct jobs among the walked tasks */
+  int32_t jobs_short;       /* of them, the jobs whose gang is ready now (ready_num >= min_available,
+                               gang.go:44-78; Pipelined counts) and would not be after losing their
+                               unplaced walked tasks */
+  int32_t affinity_now;     /* the session has pod affinity: today's verdict is applied to every step */
+  int32_t panic_nodes;      /* live nil-Node nodes: they take nothing */
+  int32_t place_off;        /* index of its first entry in `places`, -1 when places == NULL */
+  int32_t reserved[1];
+} kbg_node_drain_row; /* (the tag is the call's name, as kbg_job_fit_row) */
+/* out[i] describes nodes[i] (duplicates allowed); nodes == NULL describes
+ * every node (n_nodes must be the node count). A node or cordon index out of
+ * range and a limit outside [1, KBG_FIT_MAX_LIMIT] are KBG_E_INVALID. `places`,
+ * places_cap, *n_places and KBG_E_CAPACITY as in kbg_job_fit: each row's
+ * `walked` entries in walk order from its place_off. Everything else as
+ * kbg_job_fit: a session opened with kbg_options.reasons, KBG_E_UNSUPPORTED
+ * over a communicator or without a device. The call changes nothing: every
+ * later action returns what it would have. */
+kbg_status kbg_node_drain(kbg_session* s, const int32_t* nodes, int32_t n_nodes, const int32_t* cordon,
+                          int32_t n_cordon, int32_t limit, kbg_node_drain_row* out, kbg_fit_place* places,
+                          int32_t places_cap, int32_t* n_places);
 kbg_status kbg_node_state_get(kbg_session* s, int32_t node, kbg_node_state* out);
 kbg_status kbg_stats_get(kbg_session* s, kbg_stats* out);
 

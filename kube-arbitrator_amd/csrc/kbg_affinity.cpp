@@ -222,6 +222,88 @@ bool aff_ok(const Session& S, const AffState& st, int32_t c, int32_t n) {
   return true;
 }
 
+// aff_ok for a pod spec that has no class of the session's (kbg_node_drain: a
+// pod that runs on a node is no allocate or backfill candidate): the same three
+// rules, (A), (B) and (C) above, from the compiled terms of M.specs and the
+// AllocatedStatus pods themselves, given as (spec, node; node -1: outside the
+// session) pairs, in place of the per-class counts. ok[n] for every node.
+void aff_spec_verdicts(const Session& S, int32_t spec, const std::vector<std::pair<int32_t, int32_t>>& pods,
+                       std::vector<char>* ok) {
+  const AffinityModel& M = *S.affm;
+  const int32_t N = S.n_nodes;
+  ok->assign(N, 1);
+  int32_t allocated = 0;
+  for (const auto& [e, m] : pods) {
+    ++allocated;
+    if (e >= 0 && M.spec_poison[e]) {  // an existing pod's anti term fails to build: every node fails
+      ok->assign(N, 0);
+      return;
+    }
+  }
+  if (spec < 0) return;  // (a pod without a spec selects nothing and, as in aff_place, is selected by nothing)
+  const AffSpec& sp = M.specs[spec];
+  // the values of `keys` on node n; false where one is missing
+  auto values = [&](int32_t n, const std::vector<int32_t>& keys, std::vector<int32_t>* out) {
+    out->clear();
+    for (int32_t key : keys) {
+      const int32_t* v = find_label(M.node_labels[n], key);
+      if (!v) return false;
+      out->push_back(*v);
+    }
+    return true;
+  };
+  // (A) the pairs existing pods' anti terms forbid to this pod
+  std::vector<int64_t> forbidden;
+  for (const auto& [e, m] : pods) {
+    if (e < 0 || m < 0) continue;
+    const AffSpec& es = M.specs[e];
+    for (const AffTerm& t : es.anti) {
+      if (t.sel.err || !term_matches(t, es.ns, sp)) continue;
+      const int32_t* v = find_label(M.node_labels[m], t.key);
+      if (v) forbidden.push_back(pair_key(t.key, *v));
+    }
+  }
+  // (B) and (C): the topology values of the pods this pod's terms select
+  bool b_empty_key = false;
+  std::vector<int32_t> b_keys, c_keys, vals;
+  for (const AffTerm& t : sp.aff) {
+    if (t.key_empty) b_empty_key = true;
+    b_keys.push_back(t.key);
+  }
+  for (const AffTerm& t : sp.anti) {
+    if (t.key_empty) break;
+    c_keys.push_back(t.key);
+  }
+  const bool hasB = !sp.aff.empty(), hasC = !sp.anti.empty();
+  const bool b_self = hasB && !sp.aff_err && all_terms_match(sp.aff, sp.ns, sp);
+  int32_t nB = 0;
+  std::vector<std::vector<int32_t>> b_sigs, c_sigs;
+  for (const auto& [e, m] : pods) {
+    if (e < 0 || m < 0) continue;
+    if (hasB && !sp.aff_err && all_terms_match(sp.aff, sp.ns, M.specs[e])) {
+      ++nB;
+      if (!b_empty_key && values(m, b_keys, &vals)) b_sigs.push_back(vals);
+    }
+    if (hasC && !sp.anti_err && all_terms_match(sp.anti, sp.ns, M.specs[e]) && values(m, c_keys, &vals))
+      c_sigs.push_back(vals);
+  }
+  for (int32_t n = 0; n < N; ++n) {
+    bool v = true;
+    for (const auto& kv : M.node_labels[n])
+      v = v && std::find(forbidden.begin(), forbidden.end(), pair_key(kv.first, kv.second)) == forbidden.end();
+    if (v && hasB) {
+      if (sp.aff_err) v = false;
+      else if (nB == 0) v = b_self;
+      else v = !b_empty_key && values(n, b_keys, &vals) && std::find(b_sigs.begin(), b_sigs.end(), vals) != b_sigs.end();
+    }
+    if (v && hasC) {
+      if (sp.anti_err) v = allocated == 0;
+      else if (values(n, c_keys, &vals)) v = std::find(c_sigs.begin(), c_sigs.end(), vals) == c_sigs.end();
+    }
+    (*ok)[n] = v ? 1 : 0;
+  }
+}
+
 // The podLister's FilteredList(nodeInfo.Filter) (predicates.go:67-89) for
 // node n: a pod whose informer Spec.NodeName is n but that n's pods lack
 // (vendor cache/node_info.go:692-702) is not in the list n's predicate sees.

@@ -662,4 +662,67 @@ hipError_t launch_node_why_init(int32_t* out, int32_t ostride, int32_t n_words, 
 hipError_t launch_node_why(const NodeWhyArgs& a, hipStream_t stream, hipEvent_t start = nullptr,
                            hipEvent_t stop = nullptr);
 
+// Where a node's running pods would land if it left (kbg_node_drain). Each of
+// n_walks walks is launch_job_fit's walk (the view, the stages, LE, the
+// subtraction, `prev`, `out`, tab_lo a multiple of 64: all as JobFitArgs says)
+// with three differences.
+// - Exclusion. walk_row[w] is the table row (node - tab_lo) that takes nothing
+//   in walk w: the drained node. A row outside [0, tab_n) excludes nothing (the
+//   node belongs to another range), and -1 is the way to say so. `excl` is one
+//   plane of W words over the global nodes, common to the launch: a set bit
+//   takes nothing in any walk (the cordon). Both hold with cap_check 0. They
+//   are and-ed out of the word's `valid` as `live` is and-ed in, so an excluded
+//   node is never a candidate and never enters the view.
+// - BestEffort. A shape with kTaskShapeBestEffort goes to the lowest node that
+//   passes the stages, with no resource test (backfill.go:47-64): kind 0,
+//   ntasks += 1, Idle -= req (Resreq.IsEmpty(): every dimension below its min,
+//   mostly zero; node_info.go:108-118 subtracts it all the same).
+// - The steps of a walk may be of any mix of shapes and classes: that is what
+//   a drain is. The cursor is job fit's: a BestEffort shape keeps it (a view
+//   only gains pods), a shape with a negative request dimension never has one.
+// h_shapes, h_steps, h_walk_off and h_walk_row are the host's copies of the
+// staged arrays. launch_drain refuses (hipErrorInvalidValue, nothing launched)
+// what launch_job_fit refuses except a BestEffort shape, and also a walk_row
+// below -1 and more than kDrainMaxWalks walks.
+// n_walks <= 0 or tab_n <= 0 is a successful no-op.
+constexpr int32_t kDrainMaxWalks = 1 << 20;
+struct DrainArgs {
+  const double* nodes;  // the node table block (FirstFitArgs.nodes)
+  int32_t stride, W, tab_lo, tab_n;
+  const uint64_t *sel_ok, *taint_ok, *unsched, *live;  // StagePlanes
+  const uint64_t* excl;                                // [W] staged in device memory
+  const TaskShape* shapes;                             // [n_shapes] staged in device memory
+  const JobFitStep* steps;                             // [walk_off[n_walks]] staged in device memory
+  const int32_t* walk_off;                             // [n_walks + 1] staged in device memory
+  const int32_t* walk_row;                             // [n_walks] staged in device memory
+  int32_t n_shapes, n_walks, cap_check;
+  int32_t* out;  // [walk_off[n_walks]][2]
+  const TaskShape* h_shapes;
+  const JobFitStep* h_steps;
+  const int32_t* h_walk_off;
+  const int32_t* h_walk_row;
+};
+// What launch_drain refuses, named; nullptr for a legal launch.
+inline const char* drain_refusal(const DrainArgs& a) {
+  if (a.tab_n > kFitMaxNodes) return "table range past the touched-word bitmap";
+  if (a.n_walks > kDrainMaxWalks) return "more than 2^20 walks";
+  if (a.n_walks <= 0 || a.tab_n <= 0) return nullptr;
+  if (!a.h_shapes || !a.h_steps || !a.h_walk_off || !a.h_walk_row) return "null host copy";
+  if (a.h_walk_off[0] != 0) return "walk_off does not start at 0";
+  for (int32_t j = 0; j < a.n_walks; ++j) {
+    const int32_t s0 = a.h_walk_off[j], ns = a.h_walk_off[j + 1] - s0;
+    if (ns < 0) return "walk_off descends";
+    if (ns > kFitMaxSteps) return "a walk of more than 512 steps";
+    if (a.h_walk_row[j] < -1) return "a drained row below -1";
+    for (int32_t i = 0; i < ns; ++i) {
+      const JobFitStep& st = a.h_steps[s0 + i];
+      if (st.shape < 0 || st.shape >= a.n_shapes) return "shape index outside n_shapes";
+      if (st.prev < -1 || st.prev >= i || (st.prev >= 0 && a.h_steps[s0 + st.prev].shape != st.shape))
+        return "prev is not an earlier step of the same walk and shape";
+    }
+  }
+  return nullptr;
+}
+hipError_t launch_drain(const DrainArgs& a, hipStream_t stream, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+
 }  // namespace kbg

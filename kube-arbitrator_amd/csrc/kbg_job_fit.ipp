@@ -22,9 +22,43 @@ struct FitView {
   Res idle, rel;
   int32_t nt;
   std::vector<uint64_t> ports;  // [PW] with host ports
+  std::vector<int32_t> joined;  // kbg_node_drain: the caller's classes with host ports the walk placed here
 };
+// The host ports of kbg_node_drain's own classes (kbg_drain.ipp): per class the
+// wanted (ip, protocol, port) entries as host_ports.go compares them, and, in a
+// session that keeps port atoms, the atoms each class conflicts with.
+struct RawPort {
+  std::string ip, proto;
+  int32_t port;
+};
+inline bool port_conflict(const RawPort& a, const RawPort& b) {  // host_ports.go CheckConflict
+  return a.proto == b.proto && a.port == b.port && (a.ip == "0.0.0.0" || b.ip == "0.0.0.0" || a.ip == b.ip);
+}
+struct DrainPorts {
+  std::vector<std::vector<RawPort>> want;  // [class]
+  std::vector<uint64_t> conf;              // [class][PW], with S.has_ports
+};
+inline RawPort raw_port(const Session& S, const kbg_host_port& hp) {
+  return RawPort{S.strs[hp.host_ip].empty() ? std::string("0.0.0.0") : S.strs[hp.host_ip],
+                 S.strs[hp.protocol].empty() ? std::string("TCP") : S.strs[hp.protocol], hp.host_port};
+}
+// kbg_node_drain's walk is this one with two more rules (kbg_drain.ipp):
+// `excl` (a plane over the nodes, or null) and `xnode` (or -1) take nothing,
+// with the predicates plugin off as well, and a task with an empty request
+// goes to the first node past the stages with no resource test
+// (backfill.go:47-64). kbg_job_fit passes neither and walks no such task.
+// `cls_of` gives each step a class of the caller's own planes `sp` in place of
+// the session's, and `dports` those classes' host ports: a node's used ports
+// are the session's atoms of now (or, in a session that keeps none, the
+// entries of its pods at open: no candidate wants a port, so no action changes
+// them), and the ports of the walk's own placements join them in the view
+// (predicates.go:143-155). `aff_cls` holds those classes' pod affinity verdicts
+// of now per node, applied to every step.
 void host_job_fit(Session& S, const kbg::StagePlanes& sp, const kbg::AffState* aff, const std::vector<int32_t>& walk,
-                  kbg_fit_place* places) {
+                  kbg_fit_place* places, const uint64_t* excl = nullptr, int32_t xnode = -1,
+                  const int32_t* cls_of = nullptr, const DrainPorts* dports = nullptr,
+                  const std::vector<std::vector<char>>* aff_cls = nullptr) {
+  const bool ports = S.has_ports && !cls_of, affinity = S.has_aff && !cls_of;
   std::unordered_map<int32_t, FitView> view;
   std::unordered_set<int64_t> keys;  // (node << 32 | key) the walk added
   std::map<std::tuple<int32_t, uint64_t, uint64_t, uint64_t>, int32_t> cursor;  // n_nodes: nowhere
@@ -34,15 +68,17 @@ void host_job_fit(Session& S, const kbg::StagePlanes& sp, const kbg::AffState* a
     return u;
   };
   for (size_t i = 0; i < walk.size(); ++i) {
-    const int32_t t = walk[i], cls = S.task_class[t];
+    const int32_t t = walk[i], cls = cls_of ? cls_of[i] : S.task_class[t];
     const Res& q = S.treq[t];
     int32_t* from = q.c < 0 || q.m < 0 || q.g < 0 ? nullptr : &cursor[std::make_tuple(cls, bits(q.c), bits(q.m), bits(q.g))];
     const bool hot = S.has_dupkeys && S.key_hot[S.task_key[t]];
+    const bool beff = kbg::res_empty(q);
     kbg_fit_place& o = places[i];
     o = kbg_fit_place{t, -1, KBG_KIND_ALLOCATE, 0};
     for (int32_t n = from ? *from : 0; n < S.n_nodes; ++n) {
       const uint64_t bit = 1ull << (n & 63);
       if (!(sp.live[n >> 6] & bit)) continue;
+      if (n == xnode || (excl && (excl[n >> 6] & bit))) continue;
       if (S.panic_node[n]) continue;  // predicates.go:122-123
       const auto it = view.find(n);
       const FitView* v = it == view.end() ? nullptr : &it->second;
@@ -50,18 +86,40 @@ void host_job_fit(Session& S, const kbg::StagePlanes& sp, const kbg::AffState* a
         const size_t w = (size_t)cls * S.W + (n >> 6);
         if ((v ? v->nt : S.ntasks[n]) >= S.maxtasks[n]) continue;
         if (!(sp.sel_ok[w] & bit)) continue;
-        if (S.has_ports) {
+        if (ports) {
           const uint64_t* np = v ? v->ports.data() : &S.node_ports[(size_t)n * S.PW];
           bool conflict = false;
           for (int32_t pw = 0; pw < S.PW; ++pw) conflict = conflict || (np[pw] & S.cls_conf[(size_t)cls * S.PW + pw]);
           if (conflict) continue;
         }
+        if (dports && !dports->want[cls].empty()) {
+          const std::vector<RawPort>& want = dports->want[cls];
+          bool conflict = false;
+          if (S.has_ports) {
+            for (int32_t pw = 0; pw < S.PW; ++pw)
+              conflict = conflict || (S.node_ports[(size_t)n * S.PW + pw] & dports->conf[(size_t)cls * S.PW + pw]);
+          } else {
+            const kbg_node& nd = S.nodes_in[n];
+            for (int32_t k = 0; k < nd.port_len && !conflict; ++k) {
+              const kbg_host_port& hp = S.ports_in[nd.port_off + k];
+              if (hp.host_port <= 0) continue;
+              const RawPort used = raw_port(S, hp);
+              for (const RawPort& a : want) conflict = conflict || port_conflict(a, used);
+            }
+          }
+          for (size_t k = 0; v && k < v->joined.size() && !conflict; ++k)
+            for (const RawPort& b : dports->want[v->joined[k]])
+              for (const RawPort& a : want) conflict = conflict || port_conflict(a, b);
+          if (conflict) continue;
+        }
         if (sp.unsched[n >> 6] & bit) continue;
         if (!(sp.taint_ok[w] & bit)) continue;
-        if (S.has_aff && !kbg::aff_ok(S, *aff, cls, n)) continue;
+        if (affinity && !kbg::aff_ok(S, *aff, cls, n)) continue;
+        if (aff_cls && !(*aff_cls)[cls][n]) continue;  // the caller's classes: today's verdict (predicates.go:185-198)
       }
       int32_t kind;
-      if (kbg::res_le(q, v ? v->idle : S.idle[n])) kind = KBG_KIND_ALLOCATE;  // allocate.go:136-146
+      if (beff) kind = KBG_KIND_ALLOCATE;  // backfill.go:47-64: no resource test
+      else if (kbg::res_le(q, v ? v->idle : S.idle[n])) kind = KBG_KIND_ALLOCATE;  // allocate.go:136-146
       else if (kbg::res_le(q, v ? v->rel : S.rel[n])) kind = KBG_KIND_PIPELINE;  // allocate.go:148-162
       else continue;
       o.node = n;
@@ -71,15 +129,16 @@ void host_job_fit(Session& S, const kbg::StagePlanes& sp, const kbg::AffState* a
       FitView& u = view[n];
       if (!v) {
         u.idle = S.idle[n], u.rel = S.rel[n], u.nt = S.ntasks[n];
-        if (S.has_ports) u.ports.assign(&S.node_ports[(size_t)n * S.PW], &S.node_ports[(size_t)n * S.PW] + S.PW);
+        if (ports) u.ports.assign(&S.node_ports[(size_t)n * S.PW], &S.node_ports[(size_t)n * S.PW] + S.PW);
       }
       if (!S.nil_node[n]) {
         Res& x = kind == KBG_KIND_ALLOCATE ? u.idle : u.rel;
         x.c -= q.c, x.m -= q.m, x.g -= q.g;  // Resource.Sub, plain fp64 (resource_info.go:100-110)
       }
       u.nt++;
-      if (S.has_ports)
+      if (ports)
         for (int32_t pw = 0; pw < S.PW; ++pw) u.ports[pw] |= S.cls_add[(size_t)cls * S.PW + pw];
+      if (dports && !dports->want[cls].empty()) u.joined.push_back(cls);
       if (hot) keys.insert(nk);
       break;
     }

@@ -1863,6 +1863,119 @@ hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t st
   return hipGetLastError();
 }
 
+// --------------------------------------------------------- node drain walk
+// kbg_node_drain: where the pods a node holds would land one after the other
+// if the node took nothing (kbg_device.hpp DrainArgs). The geometry is
+// kbg_job_fit_kernel's: one wave per walk and one wave per workgroup, a lane
+// per node of the current 64-node word, the view an LDS overlay of the touched
+// nodes (at most one entry per step) with a touched-word bitmap, no workgroup
+// barrier. What differs sits on the scalar unit: the launch's `excl` word and
+// the walk's own row leave `valid` where `live` enters it, so an excluded node
+// is never a candidate and never gets an overlay entry; a BestEffort shape
+// takes the lowest bit of `pass` itself and skips the two LessEqual ballots; its
+// entry counts the pod and loses the request, every dimension of it below min.
+// The LDS is the job fit kernel's 32.3 KiB per workgroup: the 160 KiB of a CU
+// hold four such workgroups, so a CU runs four walks at once, one wave per
+// SIMD (occupancy 1 of 8 wave slots per SIMD; the walk is a serial chain of
+// dependent loads and ballots, and the launch's parallelism is its walks).
+__global__ __launch_bounds__(64) void kbg_drain_kernel(DrainArgs a) {
+  __shared__ double s_val[kFitMaxSteps * 6];  // Idle c/m/g, Releasing c/m/g of an entry
+  __shared__ int32_t s_row[kFitMaxSteps];     // its table row
+  __shared__ int32_t s_nt[kFitMaxSteps];      // its pod count
+  __shared__ int32_t s_land[kFitMaxSteps];    // the table row each step landed on, -1 nowhere
+  __shared__ uint32_t s_touched[kFitMaxNodes / 64 / 32];
+  __shared__ int32_t s_slot[64];
+  const int lane = threadIdx.x;
+  const int j = blockIdx.x;
+  const int s0 = __builtin_amdgcn_readfirstlane(a.walk_off[j]);
+  const int ns = min(__builtin_amdgcn_readfirstlane(a.walk_off[j + 1]) - s0, kFitMaxSteps);
+  const int xrow = __builtin_amdgcn_readfirstlane(a.walk_row[j]);  // the drained node's row
+  const int xw = xrow >= 0 && xrow < a.tab_n ? xrow >> 6 : -1;      // its word of the table, -1: not in this range
+  const int words = (a.tab_n + 63) >> 6;
+  for (int i = lane; i < (words + 31) >> 5; i += 64) s_touched[i] = 0u;
+  fit_lds_order();
+  const size_t L = (size_t)a.stride;
+  const int32_t* ni = reinterpret_cast<const int32_t*>(a.nodes + 6 * L);
+  int n_ov = 0;  // overlay entries (wave-uniform)
+  for (int i = 0; i < ns; ++i) {
+    const int si = __builtin_amdgcn_readfirstlane(a.steps[s0 + i].shape);
+    const int prev = __builtin_amdgcn_readfirstlane(a.steps[s0 + i].prev);
+    const int cls = __builtin_amdgcn_readfirstlane(a.shapes[si].cls);
+    const bool beff = (__builtin_amdgcn_readfirstlane(a.shapes[si].flags) & kTaskShapeBestEffort) != 0;
+    const double q0 = a.shapes[si].req[0], q1 = a.shapes[si].req[1], q2 = a.shapes[si].req[2];
+    // the cursor: this shape's previous step, inclusive; nowhere stays nowhere
+    const int from = prev >= 0 ? __builtin_amdgcn_readfirstlane(s_land[prev]) : 0;
+    int land = -1, kind = 0;
+    for (int wl = from >> 6; from >= 0 && wl < words; ++wl) {
+      const int w = (a.tab_lo >> 6) + wl;           // the global word
+      const int row = wl * 64 + lane;
+      const int r = min(row, a.tab_n - 1);          // a legal row for the ragged word's lanes
+      double ic = a.nodes[r], im = a.nodes[L + r], ig = a.nodes[2 * L + r];
+      double rc = a.nodes[3 * L + r], rm = a.nodes[4 * L + r], rg = a.nodes[5 * L + r];
+      int32_t nt = ni[r];
+      const int32_t mt = ni[L + r];
+      int slot = -1;
+      if ((__builtin_amdgcn_readfirstlane(s_touched[wl >> 5]) >> (wl & 31)) & 1u) {  // (wave-uniform)
+        s_slot[lane] = -1;
+        fit_lds_order();
+        for (int e = lane; e < n_ov; e += 64)
+          if ((s_row[e] >> 6) == wl) s_slot[s_row[e] & 63] = e;  // (a node has one entry at most)
+        fit_lds_order();
+        slot = s_slot[lane];
+        if (slot >= 0) {
+          ic = s_val[slot * 6], im = s_val[slot * 6 + 1], ig = s_val[slot * 6 + 2];
+          rc = s_val[slot * 6 + 3], rm = s_val[slot * 6 + 4], rg = s_val[slot * 6 + 5];
+          nt = s_nt[slot];
+        }
+      }
+      uint64_t valid = a.live[w] & ~a.excl[w];      // the cordon takes nothing
+      if (wl == xw) valid &= ~(1ull << (xrow & 63));  // nor does the drained node
+      if (wl * 64 + 64 > a.tab_n) valid &= (1ull << (a.tab_n - wl * 64)) - 1ull;  // bits past the table's last node
+      if (wl == (from >> 6)) valid &= ~0ull << (from & 63);                        // nodes before the cursor
+      uint64_t pass = valid;
+      if (a.cap_check) {  // predicates.go:125-183
+        pass &= ~__ballot(nt >= mt) & ~a.unsched[w];
+        pass &= a.sel_ok[(size_t)cls * a.W + w] & a.taint_ok[(size_t)cls * a.W + w];
+      }
+      if (!pass) continue;  // (wave-uniform)
+      uint64_t fi = ~0ull, cand = pass;  // BestEffort: the stages alone (backfill.go:47-64)
+      if (!beff) {
+        fi = fit_mask<false>(ic, im, ig, q0, q1, q2);
+        cand = pass & (fi | fit_mask<false>(rc, rm, rg, q0, q1, q2));
+      }
+      if (!cand) continue;
+      const int b = __builtin_ctzll(cand);
+      kind = (fi >> b) & 1ull ? 0 : 1;  // Idle first, else Releasing on the same node (allocate.go:136-162)
+      const uint64_t has = __ballot(slot >= 0);
+      const int e = (has >> b) & 1ull ? __builtin_amdgcn_readlane(slot, b) : n_ov++;
+      if (lane == b) {
+        if (kind == 0) ic -= q0, im -= q1, ig -= q2;  // Idle.Sub (node_info.go:108-118; BestEffort: below min)
+        else rc -= q0, rm -= q1, rg -= q2;            // Releasing.Sub (node_info.go:119-126)
+        s_row[e] = row;
+        s_val[e * 6] = ic, s_val[e * 6 + 1] = im, s_val[e * 6 + 2] = ig;
+        s_val[e * 6 + 3] = rc, s_val[e * 6 + 4] = rm, s_val[e * 6 + 5] = rg;
+        s_nt[e] = nt + 1;
+      }
+      if (lane == 0) s_touched[wl >> 5] |= 1u << (wl & 31);
+      land = wl * 64 + b;
+      break;
+    }
+    if (lane == 0) {
+      s_land[i] = land;
+      a.out[2 * (size_t)(s0 + i)] = land < 0 ? -1 : a.tab_lo + land;
+      a.out[2 * (size_t)(s0 + i) + 1] = kind;
+    }
+    fit_lds_order();
+  }
+}
+
+hipError_t launch_drain(const DrainArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (drain_refusal(a)) return hipErrorInvalidValue;
+  if (a.n_walks <= 0 || a.tab_n <= 0) return hipSuccess;
+  hipExtLaunchKernelGGL(kbg_drain_kernel, dim3(a.n_walks), dim3(64), 0, stream, start, stop, 0, a);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------- node reasons
 // kbg_node_reasons: the table of kbg_task_why_kernel reduced along the other
 // axis (kbg_device.hpp NodeWhy). Its geometry: a wave owns one 64-node word,

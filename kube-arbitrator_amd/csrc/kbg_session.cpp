@@ -786,6 +786,11 @@ void free_device(Session& S) {
   S.d_nwhy_shapes = nullptr;  // (d_allocs too)
   S.d_nwhy_words = S.d_nwhy_out = nullptr;
   S.nwhy_shape_cap = S.nwhy_word_cap = 0;
+  S.d_drain_shapes = nullptr;  // (d_allocs too)
+  S.d_drain_steps = nullptr;
+  S.d_drain_off = S.d_drain_row = S.d_drain_out = nullptr;
+  S.d_drain_excl = nullptr;
+  S.drain_shape_cap = S.drain_step_cap = S.drain_walk_cap = S.drain_excl_cap = 0;
   for (auto& e : S.why_ev)
     if (e) {
       (void)hipEventDestroy(e);
@@ -1109,6 +1114,8 @@ kbg_status device_scan(Session& S, kbg::Stage& sg, int32_t G, int32_t base) {
 #include "kbg_job_fit.ipp"  // kbg_job_fit: where a job's Pending tasks would land now
 
 #include "kbg_node_why.ipp"  // kbg_node_reasons: which Pending tasks a node would take now
+
+#include "kbg_drain.ipp"  // kbg_node_drain: where a node's running pods would land if it left
 
 #include "kbg_update.ipp"  // resident session updates (kbg_session_update)
 
@@ -1501,6 +1508,20 @@ kbg_status kbg_node_reasons(kbg_session* s, const int32_t* nodes, int32_t n_node
   if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
   try {
     return node_reasons(s->s, nodes, n_nodes, out);
+  } catch (const std::bad_alloc&) {
+    return fail(KBG_E_NOMEM, "host allocation failed");
+  } catch (const std::exception& e) {
+    return fail(KBG_E_INVALID, std::string("internal: ") + e.what());
+  }
+}
+
+kbg_status kbg_node_drain(kbg_session* s, const int32_t* nodes, int32_t n_nodes, const int32_t* cordon, int32_t n_cordon,
+                          int32_t limit, kbg_node_drain_row* out, kbg_fit_place* places, int32_t places_cap,
+                          int32_t* n_places) {
+  if (kbg_status st_ = usable(s); st_ != KBG_OK) return st_;
+  if (s->s.stream) HIP_TRY(hipSetDevice(s->s.device));
+  try {
+    return node_drain(s->s, nodes, n_nodes, cordon, n_cordon, limit, out, places, places_cap, n_places);
   } catch (const std::bad_alloc&) {
     return fail(KBG_E_NOMEM, "host allocation failed");
   } catch (const std::exception& e) {

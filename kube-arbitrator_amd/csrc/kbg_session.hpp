@@ -604,6 +604,12 @@ struct Session {
   kbg::NodeWhyShape* d_nwhy_shapes = nullptr;
   int32_t *d_nwhy_words = nullptr, *d_nwhy_out = nullptr;
   size_t nwhy_shape_cap = 0, nwhy_word_cap = 0;       // shape records / words (64 slots of every plane each)
+  // kbg_node_drain: the staged shapes, steps, walk offsets, drained rows, excluded plane and places (HBM, grown on demand)
+  kbg::TaskShape* d_drain_shapes = nullptr;
+  kbg::JobFitStep* d_drain_steps = nullptr;
+  int32_t *d_drain_off = nullptr, *d_drain_row = nullptr, *d_drain_out = nullptr;
+  uint64_t* d_drain_excl = nullptr;
+  size_t drain_shape_cap = 0, drain_step_cap = 0, drain_walk_cap = 0, drain_excl_cap = 0;
 
   // ---- NodeInfo.Tasks keys (node_info.go:101-106): AddTask of a PodKey the
   // node already holds returns an error and leaves the node unchanged, while
@@ -681,10 +687,16 @@ bool parse_go_int64(const std::string& s, int64_t* out);
 bool label_key_valid(const std::string& k);    // IsQualifiedName (validation.go:42-70)
 bool label_value_valid(const std::string& v);  // IsValidLabelValue (validation.go:97-106)
 void compile_static_predicates(Session& S, StaticHost* out);
+// The tables of a class list of the caller's, one class per entry (a spec
+// index, -1: no spec); S is left as it is (kbg_node_drain).
+void compile_spec_classes(Session& S, const std::vector<int32_t>& class_spec, StaticHost* out);
 // kbg_affinity.cpp
 void setup_affinity(Session& S);
 void aff_place(Session& S, int32_t t, int32_t n, int32_t sign, AffState& st, bool update_bits);
 bool aff_ok(const Session& S, const AffState& st, int32_t c, int32_t n);
+// aff_ok per node for a pod spec without a class of the session's, from the AllocatedStatus pods (spec, node)
+void aff_spec_verdicts(const Session& S, int32_t spec, const std::vector<std::pair<int32_t, int32_t>>& pods,
+                       std::vector<char>* ok);
 // aff_ok of the session's live state with the podLister Filter of node n applied
 bool aff_ok_node(Session& S, int32_t c, int32_t n);
 // the pod-affinity bits of every class on node n (its filtered pods changed)

@@ -322,56 +322,14 @@ std::string spec_key(const Session& S, const kbg_spec* sp) {
 
 }  // namespace
 
-// Builds classes for every pending task (allocate and backfill candidates), the node bitsets and the device
-// programs; fills S.task_class and S.static_host (uploaded by the caller).
-void compile_static_predicates(Session& S, StaticHost* out) {
-  Compiler C(S);
-  out->n_classes = 0;
-  S.task_class.assign(S.n_tasks, 0);
-  S.class_spec.assign(1, -1);
-  if (!S.pred_active) {
-    ClassProg c{};
-    c.sel_req = -1;
-    c.always = 1;
-    C.classes.push_back(c);
-    S.spec_class.assign(S.specs_in.size(), 0);
-    S.nospec_class = 0;
-  } else {
-    std::unordered_map<std::string, int32_t> class_of_key;
-    std::vector<int32_t> class_spec;
-    // a spec's class is its key's: each spec's key is built once (the tasks
-    // share a few specs), classes numbered in order of their first task
-    std::vector<int32_t> memo(S.specs_in.size() + 1, -1);  // [spec + 1] -> class; [0]: no spec
-    for (int32_t t = 0; t < S.n_tasks; ++t) {
-      if (!S.pending_candidate[t] && !S.be_task[t]) continue;  // allocate and backfill candidates
-      const int32_t sp = S.tasks_in[t].spec;
-      int32_t& m = memo[(size_t)(sp + 1)];
-      if (m < 0) {
-        const kbg_spec* spec = sp >= 0 ? &S.specs_in[sp] : nullptr;
-        std::string key = spec_key(S, spec);
-        auto it = class_of_key.find(key);
-        if (it == class_of_key.end()) {
-          const int32_t id = (int32_t)class_spec.size();
-          class_of_key.emplace(std::move(key), id);
-          class_spec.push_back(sp);
-          m = id;
-        } else {
-          m = it->second;
-        }
-      }
-      S.task_class[t] = m;
-    }
-    if (class_spec.empty()) class_spec.push_back(-1);
-    S.class_spec = class_spec;
-    // the class of every spec (for tasks that become candidates in a session
-    // update): a spec whose key no candidate had at compile time has none
-    S.spec_class.assign(S.specs_in.size(), -1);
-    for (size_t sp = 0; sp < S.specs_in.size(); ++sp) {
-      auto it = class_of_key.find(spec_key(S, &S.specs_in[sp]));
-      if (it != class_of_key.end()) S.spec_class[sp] = it->second;
-    }
-    auto it0 = class_of_key.find(spec_key(S, nullptr));
-    S.nospec_class = it0 != class_of_key.end() ? it0->second : -1;
+namespace {
+// The class programs of `class_spec` (a spec index per class, -1: no spec;
+// null: the one always-true class is in C.classes already), the taint
+// dictionary with each class's tolerated mask, the node label bitsets, numeric
+// columns, names and flags: everything `out` holds.
+void compile_tables(Session& S, Compiler& C, const std::vector<int32_t>* class_spec_p, StaticHost* out) {
+  if (class_spec_p) {
+    const std::vector<int32_t>& class_spec = *class_spec_p;
     for (int32_t sp : class_spec) C.classes.push_back(C.compile_spec(sp >= 0 ? &S.specs_in[sp] : nullptr));
 
     // taint dictionary over NoSchedule/NoExecute taints of the session nodes
@@ -480,6 +438,72 @@ void compile_static_predicates(Session& S, StaticHost* out) {
   if (out->terms.empty()) out->terms.push_back(TermProg{0, 0});
   out->classes = C.classes;
   out->n_classes = (int32_t)C.classes.size();
+}
+}  // namespace
+
+// Builds classes for every pending task (allocate and backfill candidates), the node bitsets and the device
+// programs; fills S.task_class and S.static_host (uploaded by the caller).
+void compile_static_predicates(Session& S, StaticHost* out) {
+  Compiler C(S);
+  out->n_classes = 0;
+  S.task_class.assign(S.n_tasks, 0);
+  S.class_spec.assign(1, -1);
+  if (!S.pred_active) {
+    ClassProg c{};
+    c.sel_req = -1;
+    c.always = 1;
+    C.classes.push_back(c);
+    S.spec_class.assign(S.specs_in.size(), 0);
+    S.nospec_class = 0;
+  } else {
+    std::unordered_map<std::string, int32_t> class_of_key;
+    std::vector<int32_t> class_spec;
+    // a spec's class is its key's: each spec's key is built once (the tasks
+    // share a few specs), classes numbered in order of their first task
+    std::vector<int32_t> memo(S.specs_in.size() + 1, -1);  // [spec + 1] -> class; [0]: no spec
+    for (int32_t t = 0; t < S.n_tasks; ++t) {
+      if (!S.pending_candidate[t] && !S.be_task[t]) continue;  // allocate and backfill candidates
+      const int32_t sp = S.tasks_in[t].spec;
+      int32_t& m = memo[(size_t)(sp + 1)];
+      if (m < 0) {
+        const kbg_spec* spec = sp >= 0 ? &S.specs_in[sp] : nullptr;
+        std::string key = spec_key(S, spec);
+        auto it = class_of_key.find(key);
+        if (it == class_of_key.end()) {
+          const int32_t id = (int32_t)class_spec.size();
+          class_of_key.emplace(std::move(key), id);
+          class_spec.push_back(sp);
+          m = id;
+        } else {
+          m = it->second;
+        }
+      }
+      S.task_class[t] = m;
+    }
+    if (class_spec.empty()) class_spec.push_back(-1);
+    S.class_spec = class_spec;
+    // the class of every spec (for tasks that become candidates in a session
+    // update): a spec whose key no candidate had at compile time has none
+    S.spec_class.assign(S.specs_in.size(), -1);
+    for (size_t sp = 0; sp < S.specs_in.size(); ++sp) {
+      auto it = class_of_key.find(spec_key(S, &S.specs_in[sp]));
+      if (it != class_of_key.end()) S.spec_class[sp] = it->second;
+    }
+    auto it0 = class_of_key.find(spec_key(S, nullptr));
+    S.nospec_class = it0 != class_of_key.end() ? it0->second : -1;
+    compile_tables(S, C, &class_spec, out);
+    return;
+  }
+  compile_tables(S, C, nullptr, out);
+}
+
+// The same tables for a class list of the caller's (kbg_node_drain: the specs
+// of the pods a drain moves, which are no allocate or backfill candidates and
+// have no class of the session's). Nothing of S changes.
+void compile_spec_classes(Session& S, const std::vector<int32_t>& class_spec, StaticHost* out) {
+  Compiler C(S);
+  out->n_classes = 0;
+  compile_tables(S, C, &class_spec, out);
 }
 
 }  // namespace kbg

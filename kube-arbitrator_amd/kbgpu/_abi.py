@@ -218,6 +218,13 @@ class kbg_node_why(ctypes.Structure):
                 ("reserved", i32 * 3)]
 
 
+class kbg_node_drain(ctypes.Structure):
+    _fields_ = [("valid", i32), ("node", i32), ("tasks", i32), ("walked", i32), ("placed_idle", i32),
+                ("placed_releasing", i32), ("unplaced", i32), ("first_unplaced", i32), ("nodes_used", i32),
+                ("other_pods", i32), ("jobs_moved", i32), ("jobs_short", i32), ("affinity_now", i32),
+                ("panic_nodes", i32), ("place_off", i32), ("reserved", i32 * 1)]
+
+
 class kbg_queue_state(ctypes.Structure):
     _fields_ = [("share", f64), ("deserved", kbg_resource), ("allocated", kbg_resource), ("request", kbg_resource),
                 ("overused", i32), ("has_attr", i32)]
@@ -313,6 +320,8 @@ SIGNATURES = {
     "kbg_task_headroom": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_task_room)]),
     "kbg_job_fit": (i32, [ctypes.c_void_p, P(i32), i32, i32, P(kbg_job_fit), P(kbg_fit_place), i32, P(i32)]),
     "kbg_node_reasons": (i32, [ctypes.c_void_p, P(i32), i32, P(kbg_node_why)]),
+    "kbg_node_drain": (i32, [ctypes.c_void_p, P(i32), i32, P(i32), i32, i32, P(kbg_node_drain), P(kbg_fit_place), i32,
+                             P(i32)]),
     "kbg_node_state_get": (i32, [ctypes.c_void_p, i32, P(kbg_node_state)]),
     "kbg_stats_get": (i32, [ctypes.c_void_p, P(kbg_stats)]),
     "kbg_session_close": (None, [ctypes.c_void_p]),

@@ -166,6 +166,28 @@ def node_message(row):
     return head + (f"; turned away: {', '.join(parts)}" if parts else "")
 
 
+def drain_message(row):
+    """One line for a node an operator wants to drain (a Session.node_drain
+    row): how many of the pods it holds find room elsewhere now, from Idle and
+    from resources that are being released, on how many nodes, the first pod
+    that does not, and the gangs that would lose their minimum."""
+    if not row["valid"]:
+        return "not a live node"
+    if row["tasks"] == 0:
+        tail = f" ({row['other_pods']} other pods stay out of the walk)" if row["other_pods"] else ""
+        return "no pods to move" + tail
+    placed = row["placed_idle"] + row["placed_releasing"]
+    msg = (f"{placed} of {row['walked']} pods find room ({row['placed_releasing']} on releasing resources, "
+           f"{row['nodes_used']} nodes)")
+    if row["unplaced"]:
+        msg += f"; {row['unplaced']} do not, first task {row['first_unplaced']}"
+    if row["jobs_short"]:
+        msg += f"; breaks {row['jobs_short']} gang" + ("s" if row["jobs_short"] > 1 else "")
+    msg += f"; {row['tasks'] - row['walked']} not walked" if row["tasks"] > row["walked"] else ""
+    msg += " (pod affinity as it is now)" if row["affinity_now"] else ""
+    return msg
+
+
 def reasons_row(st):
     """A kbg_job_reasons as the output rows carry it."""
     return {"task": st.task, "before": st.before, "visited": st.visited, "count": list(st.count),

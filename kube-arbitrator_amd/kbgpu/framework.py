@@ -754,6 +754,40 @@ class Session:
                  "first_task": list(r.first_task), "idle_short": list(r.idle_short), "open_idle": r.open_idle,
                  "open_releasing": r.open_releasing, "idle_best_effort": r.idle_best_effort} for r in out[:n]]
 
+    def node_drain(self, nodes=None, cordon=(), limit=_abi.FIT_MAX_LIMIT):
+        """One dict per node (the indices `nodes`, duplicates allowed, or every
+        node): where the pods it holds now, the first `limit` (1..512) in
+        NodeInfo.Tasks order, would land if the node and every node of
+        `cordon` took nothing, each on its first fitting node of a view in
+        which the pods before it have taken their share (kbg_node_drain).
+        `places` holds (task, node, kind) per walked task, node -1 for a task
+        no node takes. Legal any time after open on sessions opened with
+        reasons=True; changes nothing."""
+        if nodes is None:
+            n, arr = len(self.flat.node_names), None
+        else:
+            n, arr = len(nodes), (ctypes.c_int32 * max(len(nodes), 1))(*nodes)
+        cordon = list(cordon)
+        carr = (ctypes.c_int32 * len(cordon))(*cordon) if cordon else None
+        out = (_abi.kbg_node_drain * max(n, 1))()
+        need = ctypes.c_int32(0)
+        L = _abi.lib()
+        # one call: a buffer for `limit` places per row, or every task per row where that is less
+        cap = max(1, n * min(int(limit) if 1 <= int(limit) <= _abi.FIT_MAX_LIMIT else 1, len(self.flat.task_objs)))
+        places = (_abi.kbg_fit_place * cap)()
+        _abi.check(L.kbg_node_drain(self.handle, arr, n, carr, len(cordon), int(limit), out, places, cap,
+                                    ctypes.byref(need)))
+        keys = ("node", "tasks", "walked", "placed_idle", "placed_releasing", "unplaced", "first_unplaced",
+                "nodes_used", "other_pods", "jobs_moved", "jobs_short", "panic_nodes")
+        rows = []
+        for r in out[:n]:
+            row = {"valid": bool(r.valid), **{k: getattr(r, k) for k in keys}, "affinity_now": bool(r.affinity_now),
+                   "places": []}
+            if r.valid:
+                row["places"] = [(p.task, p.node, p.kind) for p in places[r.place_off:r.place_off + r.walked]]
+            rows.append(row)
+        return rows
+
     def queue_state(self, q):
         st = _abi.kbg_queue_state()
         _abi.check(_abi.lib().kbg_queue_state_get(self.handle, q, ctypes.byref(st)))

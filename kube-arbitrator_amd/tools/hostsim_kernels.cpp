@@ -785,6 +785,55 @@ void job_fit_run(const JobFitArgs& a) {
   }
 }
 
+// ---- node drain walk (kbg_device.hpp DrainArgs): job_fit_run's walk with the
+// launch's excluded plane, each walk's own excluded row and BestEffort steps.
+void drain_run(const DrainArgs& a) {
+  const Table t = table_of(a.nodes, a.stride);
+  struct View {
+    double idle[3], rel[3];
+    int32_t nt;
+  };
+  for (int32_t j = 0; j < a.n_walks; ++j) {
+    const int32_t s0 = a.walk_off[j], ns = a.walk_off[j + 1] - s0, xrow = a.walk_row[j];
+    std::map<int32_t, View> view;
+    std::vector<int32_t> land(ns, -1);
+    for (int32_t i = 0; i < ns; ++i) {
+      const JobFitStep& st = a.steps[s0 + i];
+      const TaskShape& sh = a.shapes[st.shape];
+      const bool beff = (sh.flags & kTaskShapeBestEffort) != 0;
+      int32_t at = -1, kind = 0;
+      const int32_t from = st.prev >= 0 ? land[st.prev] : 0;
+      for (int32_t row = from; from >= 0 && row < a.tab_n; ++row) {
+        const int32_t n = a.tab_lo + row;
+        const uint64_t bit = 1ull << (n & 63);
+        if (!(a.live[n >> 6] & bit) || (a.excl[n >> 6] & bit) || row == xrow) continue;
+        View v{{t.ic[row], t.im[row], t.ig[row]}, {t.rc[row], t.rm[row], t.rg[row]}, t.nt[row]};
+        const auto it = view.find(row);
+        if (it != view.end()) v = it->second;
+        if (a.cap_check) {  // predicates.go:125-183
+          if (v.nt >= t.mt[row]) continue;
+          if (!(a.sel_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) continue;
+          if (a.unsched[n >> 6] & bit) continue;
+          if (!(a.taint_ok[(size_t)sh.cls * a.W + (n >> 6)] & bit)) continue;
+        }
+        double* x = nullptr;
+        if (beff) x = v.idle, kind = 0;  // backfill.go:47-64: no resource test
+        else if (fits(false, sh.req, v.idle[0], v.idle[1], v.idle[2])) x = v.idle, kind = 0;  // allocate.go:136-146
+        else if (fits(false, sh.req, v.rel[0], v.rel[1], v.rel[2])) x = v.rel, kind = 1;  // allocate.go:148-162
+        if (!x) continue;
+        for (int d = 0; d < 3; ++d) x[d] -= sh.req[d];
+        v.nt++;
+        view[row] = v;
+        at = row;
+        break;
+      }
+      land[i] = at;
+      a.out[2 * (size_t)(s0 + i)] = at < 0 ? -1 : a.tab_lo + at;
+      a.out[2 * (size_t)(s0 + i) + 1] = at < 0 ? 0 : kind;
+    }
+  }
+}
+
 void node_delta_run(const NodeSoA& n, const NodeDelta& d) {
   n.idle_cpu[d.node] = d.idle[0];
   n.idle_mem[d.node] = d.idle[1];
@@ -824,13 +873,14 @@ enum Count : int {
   kCountTaskHeadroom,
   kCountStageMask,
   kCountNodeWhy,  // (ahead of the last two: tests/test_hostsim_job_fit.py names the list's end)
+  kCountDrain,    // (after node_why, for the same reason)
   kCountVictimWhy,
   kCountJobFit,
   kCounts
 };
 constexpr const char* kCountNames =
     "victim_scan,victim_big,victim_big_row_out,victim_prep,victim_prep_next_chunk,victim_prep_inline,"
-    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,node_why,victim_why,job_fit";
+    "victim_prep_inline_nodes,victim_prep_inline_state,task_why,task_headroom,stage_mask,node_why,drain,victim_why,job_fit";
 std::atomic<int64_t> g_count[kCounts];
 // Every launch of this file in order, and the staged prep's last one: a
 // staged prep that directly follows a staged prep and carries node rows, or
@@ -1029,6 +1079,13 @@ hipError_t launch_job_fit(const JobFitArgs& a, hipStream_t stream, hipEvent_t st
   if (a.n_jobs <= 0 || a.tab_n <= 0) return hipSuccess;
   g_count[kCountJobFit]++;
   return launch(stream, start, stop, [a] { job_fit_run(a); });
+}
+
+hipError_t launch_drain(const DrainArgs& a, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+  if (drain_refusal(a)) return hipErrorInvalidValue;
+  if (a.n_walks <= 0 || a.tab_n <= 0) return hipSuccess;
+  g_count[kCountDrain]++;
+  return launch(stream, start, stop, [a] { drain_run(a); });
 }
 
 hipError_t launch_node_why_init(int32_t* out, int32_t ostride, int32_t n_words, hipStream_t stream) {

@@ -6,7 +6,7 @@
 //   hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions a,b,...]
 //                [--batch-tasks N] [--candidates N] [--full-scan]
 //                [--general-scan] [--repeat N] [--victim-reasons] [--job-fit]
-//                [--node-why]
+//                [--node-why] [--drain]
 //
 // Each repeat opens a session, runs the actions (reclaim, allocate, backfill,
 // preempt, in the order given), resets the session, runs them again and
@@ -27,6 +27,12 @@
 // and for a named subset (the last node, the first, the last again and every
 // 70th: duplicates, out of order, one word or several). The rows do not go to
 // OUT either; a summary goes to stderr.
+// --drain opens the session with kbg_options.reasons too and calls
+// kbg_node_drain before the first action and after each one: every node at
+// limit 512 with the places and no cordon, then a named subset (the last node,
+// the first, the last again and every 70th) at limit 2 without places, with
+// every 3rd node cordoned. The rows do not go to OUT either; a summary goes to
+// stderr.
 // Exit status 0 unless the arguments or the files are unusable.
 #include <cstdio>
 #include <cstdlib>
@@ -134,12 +140,53 @@ void node_why(kbg_session* s, const std::string& after, int32_t n_nodes) {
   fprintf(stderr, "; %lld open; %lld of %zu named rows differ\n", (long long)open, (long long)differ, pick.size());
 }
 
+// kbg_node_drain of every node, and of a named subset under a cordon; what it found, to stderr.
+void node_drain(kbg_session* s, const std::string& after, int32_t n_nodes) {
+  std::vector<kbg_node_drain_row> all((size_t)n_nodes + 1);
+  std::vector<int32_t> pick, cordon;
+  if (n_nodes > 0) pick = {n_nodes - 1, 0, n_nodes - 1};
+  for (int32_t i = 70; i < n_nodes; i += 70) pick.push_back(i);
+  for (int32_t i = 1; i < n_nodes; i += 3) cordon.push_back(i);
+  std::vector<kbg_node_drain_row> some(pick.size() + 1);
+  std::vector<kbg_fit_place> places;
+  int32_t need = 0;
+  kbg_status st = kbg_node_drain(s, nullptr, n_nodes, nullptr, 0, KBG_FIT_MAX_LIMIT, all.data(), nullptr, 0, &need);
+  if (st == KBG_OK) {
+    places.resize((size_t)need + 1);
+    st = kbg_node_drain(s, nullptr, n_nodes, nullptr, 0, KBG_FIT_MAX_LIMIT, all.data(), places.data(), need, &need);
+  }
+  if (st == KBG_OK)
+    st = kbg_node_drain(s, pick.data(), (int32_t)pick.size(), cordon.data(), (int32_t)cordon.size(), 2, some.data(),
+                        nullptr, 0, &need);
+  if (st != KBG_OK) {
+    fprintf(stderr, "hostsim_main: node drain after %s: status %d: %s\n", after.c_str(), (int)st, kbg_last_error());
+    return;
+  }
+  int64_t valid = 0, walked = 0, idle = 0, rel = 0, nowhere = 0, shrt = 0, cut = 0;
+  for (int32_t i = 0; i < n_nodes; ++i) {
+    if (!all[i].valid) continue;
+    ++valid;
+    walked += all[i].walked;
+    idle += all[i].placed_idle;
+    rel += all[i].placed_releasing;
+    shrt += all[i].jobs_short;
+    for (int32_t k = 0; k < all[i].walked; ++k) nowhere += places[(size_t)all[i].place_off + k].node < 0;
+  }
+  for (size_t k = 0; k < pick.size(); ++k) cut += some[k].valid ? some[k].unplaced : 0;
+  fprintf(stderr, "hostsim_main: node drain after %s: %lld live nodes, %lld pods walked, %lld on idle, %lld on releasing, "
+                  "%lld nowhere, %lld gangs short; %zu named rows under a cordon of %zu: %lld nowhere\n",
+          after.c_str(), (long long)valid, (long long)walked, (long long)idle, (long long)rel, (long long)nowhere,
+          (long long)shrt, pick.size(), cordon.size(), (long long)cut);
+}
+
 void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_t n_tasks, int32_t n_nodes,
-                 std::vector<char>& out, int32_t why_jobs = -1, int32_t fit_jobs = -1, bool nwhy = false) {
+                 std::vector<char>& out, int32_t why_jobs = -1, int32_t fit_jobs = -1, bool nwhy = false,
+                 bool drain = false) {
   std::vector<kbg_decision> dec((size_t)n_tasks + 1);
   int32_t n = 0;
   if (fit_jobs >= 0) job_fit(s, "open", fit_jobs);
   if (nwhy) node_why(s, "open", n_nodes);
+  if (drain) node_drain(s, "open", n_nodes);
   for (const std::string& a : actions) {
     const kbg_status st = run_action(s, a, dec.data(), (int32_t)dec.size(), &n);
     put_i32(out, (int32_t)st);
@@ -151,6 +198,7 @@ void run_actions(kbg_session* s, const std::vector<std::string>& actions, int32_
     if (why_jobs >= 0 && (a == "reclaim" || a == "preempt")) victim_reasons(s, a, why_jobs);
     if (fit_jobs >= 0) job_fit(s, a, fit_jobs);
     if (nwhy) node_why(s, a, n_nodes);
+    if (drain) node_drain(s, a, n_nodes);
   }
   // the decision log (Allocate and Pipeline decisions of every action) and the action behind each
   put_i32(out, n);
@@ -179,7 +227,7 @@ int usage() {
   fprintf(stderr,
           "usage: hostsim_main SNAPSHOT OUT [--schedule eager|lazy] [--actions reclaim,allocate,backfill,preempt]\n"
           "                    [--batch-tasks N] [--candidates N] [--full-scan] [--general-scan] [--repeat N]\n"
-          "                    [--victim-reasons] [--job-fit] [--node-why]\n"
+          "                    [--victim-reasons] [--job-fit] [--node-why] [--drain]\n"
           "  --actions: any of reclaim, allocate, backfill, preempt, run in the order given (default allocate)\n");
   return 2;
 }
@@ -192,7 +240,7 @@ int main(int argc, char** argv) {
   memset(&opts, 0, sizeof opts);
   std::vector<std::string> actions{"allocate"};
   int repeat = 1;
-  bool why = false, fit = false, nwhy = false;
+  bool why = false, fit = false, nwhy = false, drain = false;
   for (int i = 3; i < argc; ++i) {
     const std::string a = argv[i];
     const bool more = i + 1 < argc;
@@ -228,6 +276,9 @@ int main(int argc, char** argv) {
     } else if (a == "--node-why") {
       nwhy = true;
       opts.reasons = 1;
+    } else if (a == "--drain") {
+      drain = true;
+      opts.reasons = 1;
     } else if (a == "--repeat" && more) {
       repeat = atoi(argv[++i]);
     } else {
@@ -249,10 +300,12 @@ int main(int argc, char** argv) {
       fprintf(stderr, "hostsim_main: open: status %d: %s\n", (int)st, kbg_last_error());
       continue;
     }
-    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy);
+    run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy,
+                drain);
     const kbg_status rs = kbg_session_reset(s);
     put_i32(out, (int32_t)rs);
-    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy);
+    if (rs == KBG_OK) run_actions(s, actions, snap->n_tasks, snap->n_nodes, out, why ? snap->n_jobs : -1, fit ? snap->n_jobs : -1, nwhy,
+                drain);
     kbg_session_close(s);
   }
   kbg_snapshot_blob_free(blob);

@@ -1101,3 +1101,99 @@ extern "C" int32_t kbg_tool_probe_node_why(const kbg_probe_node_why* p, void* no
   PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
   return 0;
 }
+
+// kbg_drain_kernel, as kbg_node_drain runs it for n_walks walks at once.
+thread_local double t_drain_ms = 0;  // the HIP-event time of the last launch (tools/drain_bench.py)
+extern "C" double kbg_tool_probe_drain_ms() { return t_drain_ms; }
+
+struct kbg_probe_drain {
+  int32_t n_nodes, W, tab_lo, tab_n;  // the table holds the global nodes [tab_lo, tab_lo + tab_n)
+  int32_t stride;                     // rows of the node table block (row = node - tab_lo)
+  int32_t classes;                    // rows of the per-class stage planes
+  int32_t n_shapes, cap_check;
+  int32_t n_walks, n_steps;  // walk_off holds n_walks + 1 offsets, the last n_steps
+};
+
+// The arrays of kbg_tool_probe_job_fit, then the excluded plane (W words over
+// the global nodes) and each walk's excluded table row. out: n_steps * 2 words
+// + guard, device memory filled with the sentinel before the launch. What
+// launch_drain refuses is refused here by name (a table range past the bitmap
+// before any array is read). The node block and the planes are copied back so
+// the caller sees them untouched.
+extern "C" int32_t kbg_tool_probe_drain(const kbg_probe_drain* p, void* nodes, uint64_t* planes,
+                                        const kbg::TaskShape* shapes, const kbg::JobFitStep* steps,
+                                        const int32_t* walk_off, const uint64_t* excl, const int32_t* walk_row,
+                                        void* out) {
+  t_error.clear();
+  if (!p || !nodes || !shapes || !steps || !walk_off || !excl || !walk_row || !out) return reject("null argument");
+  if (!planes) return reject("null planes");
+  if (p->n_nodes < 1 || p->W < 1 || p->n_nodes > p->W * 64) return reject("n_nodes outside W");
+  if (p->tab_lo < 0 || (p->tab_lo & 63)) return reject("tab_lo not a multiple of 64");
+  if (p->tab_n < 1 || (int64_t)p->tab_lo + p->tab_n > p->n_nodes) return reject("node range outside n_nodes");
+  if (p->stride < 1 || p->tab_n > p->stride) return reject("node range outside the table block");
+  if (p->tab_n > kbg::kFitMaxNodes) return reject("table range past the touched-word bitmap");
+  if (p->classes < 1) return reject("no class");
+  if (p->n_shapes < 1 || p->n_shapes > (1 << 20)) return reject("n_shapes outside 1..2^20");
+  if (p->n_walks < 1 || p->n_walks > kbg::kDrainMaxWalks) return reject("n_walks outside 1..2^20");
+  if (p->n_steps < 0 || walk_off[0] != 0 || walk_off[p->n_walks] != p->n_steps)
+    return reject("walk_off does not span n_steps");
+  for (int32_t j = 0; j < p->n_walks; ++j)
+    if (walk_off[j] > walk_off[j + 1] || walk_off[j + 1] > p->n_steps) return reject("walk_off descends");
+  for (int32_t i = 0; i < p->n_shapes; ++i)
+    if (shapes[i].cls < 0 || shapes[i].cls >= p->classes) return reject("shape: cls outside the planes");
+
+  kbg::DrainArgs a{};
+  a.stride = p->stride;
+  a.W = p->W;
+  a.tab_lo = p->tab_lo;
+  a.tab_n = p->tab_n;
+  a.n_shapes = p->n_shapes;
+  a.n_walks = p->n_walks;
+  a.cap_check = p->cap_check ? 1 : 0;
+  a.h_shapes = shapes;
+  a.h_steps = steps;
+  a.h_walk_off = walk_off;
+  a.h_walk_row = walk_row;
+  if (const char* why = kbg::drain_refusal(a)) return reject(why);
+
+  Scope sc;
+  PROBE_TRY(hipStreamCreate(&sc.stream));
+  const size_t L = (size_t)p->stride;
+  double* d = nullptr;
+  PROBE_TRY(dev_copy(sc, (char**)&d, (const char*)nodes, L * 56));
+  uint64_t* d_planes = nullptr;
+  const size_t plane_words = kbg::kbg_stage_words(p->classes, p->W);
+  PROBE_TRY(dev_copy(sc, &d_planes, (const uint64_t*)planes, plane_words));
+  const kbg::StagePlanes sp = kbg::kbg_stage_planes(d_planes, p->classes, p->W);
+  a.nodes = d;
+  a.sel_ok = sp.sel_ok;
+  a.taint_ok = sp.taint_ok;
+  a.unsched = sp.unsched;
+  a.live = sp.live;
+  PROBE_TRY(dev_copy(sc, (uint64_t**)&a.excl, excl, (size_t)p->W));
+  PROBE_TRY(dev_copy(sc, (kbg::TaskShape**)&a.shapes, shapes, (size_t)p->n_shapes));
+  PROBE_TRY(dev_copy(sc, (kbg::JobFitStep**)&a.steps, steps, (size_t)p->n_steps));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.walk_off, walk_off, (size_t)p->n_walks + 1));
+  PROBE_TRY(dev_copy(sc, (int32_t**)&a.walk_row, walk_row, (size_t)p->n_walks));
+  const size_t out_bytes = (size_t)p->n_steps * 8 + kProbeGuardBytes;
+  PROBE_TRY(dev_copy(sc, (char**)&a.out, (const char*)nullptr, out_bytes, kProbeSentinel));
+
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  PROBE_TRY(hipEventCreate(&ev[0]));
+  if (const hipError_t e = hipEventCreate(&ev[1]); e != hipSuccess) {
+    (void)hipEventDestroy(ev[0]);
+    return hip_fail(e, "hipEventCreate");
+  }
+  hipError_t e = kbg::launch_drain(a, sc.stream, ev[0], ev[1]);
+  if (e == hipSuccess) e = hipStreamSynchronize(sc.stream);
+  float ms = 0;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  (void)hipEventDestroy(ev[0]);
+  (void)hipEventDestroy(ev[1]);
+  PROBE_TRY(e);
+  t_drain_ms = ms;
+  PROBE_TRY(hipMemcpy(out, a.out, out_bytes, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(nodes, d, L * 56, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(planes, d_planes, plane_words * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
