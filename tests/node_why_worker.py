@@ -28,7 +28,9 @@ LIB = os.path.join(ROOT, "kube-arbitrator_amd", "tools", "libkbg_hostsim.so")
 # Pending tasks are left), three a generator; affinity509 discards a statement after evicting
 SEEDS = {"random": (1, 5, 8), "contended": (6, 7, 19), "ports": (0, 1, 13), "affinity": (500, 506, 509)}
 KATS = ("kat_task_why", "kat_reclaim", "kat_preempt")
-RESIDENT = ("structural/w_grows", "in_place/regrow_keys")
+# (recompile/relabel_hand: kbg_node_reasons is the only call asked, so the first to need the stage planes after a
+# NODE_SET recompile; tests/query_update_session.py asks it among the other six)
+RESIDENT = ("structural/w_grows", "in_place/regrow_keys", "recompile/relabel_hand")
 SESSION_CASES = (["kat_node_why-hand", "refusals"] + ["resident:" + c for c in RESIDENT] + list(KATS) +
                  [f"{kind}{s}" for kind, seeds in SEEDS.items() for s in seeds])
 

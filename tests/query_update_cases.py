@@ -14,7 +14,8 @@ Every fixture has at most 70 nodes and 10 jobs of 6 tasks. The seeds were
 picked on the CPU with the oracle and the hostsim library: S0 and S1 run every
 action prefix "ok", the library takes the batch, a fixture can say S1, Pending
 tasks are left before the first action and after the last, and some row of the
-four calls differs from the warm-up's."""
+four older calls and of each of kbg_job_fit, kbg_node_reasons and
+kbg_node_drain differs from the warm-up's (tests/test_query_update_ref.py)."""
 import copy
 
 import update_events as ue
@@ -75,7 +76,7 @@ def hand_cluster(n_nodes):
     3 CPUs twice (short everywhere), `sel` wants zone c (no node). Queue q2:
     `fill` has 4 Pending 1-CPU pods that are placed, `own` 2 Pending pods that
     want zone b and tolerate the taint. After any cycle `big` and `sel` stay
-    Pending: the rows of the four calls speak of them. The oracle's preempt
+    Pending: the rows of the query calls speak of them. The oracle's preempt
     panics on this cluster (a Resource.Sub underflow of the reference), so the
     cycle is allocate and backfill."""
     nodes = [_node(i) for i in range(n_nodes)]
@@ -294,7 +295,7 @@ STRUCTURAL_SEEDS = {"random": (15, 17, 24, 34), "contended": (1, 6, 35, 72), "po
                     "affinity": (1, 13, 35, 56)}
 FUZZ_SEEDS = (1, 15, 23, 27, 45, 59)
 RELABEL_SEEDS = (4, 5, 8, 18)
-CHAIN_SEEDS = (13, 108, 167)
+CHAIN_SEEDS = (13, 108, 167, 235)  # (235: the node its structural round adds takes a kbg_job_fit or kbg_node_drain place)
 
 HAND = {"structural": (w_grows, w_shrinks, queue_delete_first_holder, pod_group_add_new_class,
                        queue_add_starves),

@@ -22,15 +22,20 @@ sys.path.insert(0, HERE)
 
 LIB = os.path.join(ROOT, "kube-arbitrator_amd", "tools", "libkbg_hostsim.so")
 KEEP = ("errors", "rows", "rows_ref", "skipped", "rebuilds", "by_uid_only", "n_classes", "answered", "launches",
-        "stage_mask", "host_only", "evicted0", "ref")
+        "stage_mask", "host_only", "evicted0", "ref", "rows_ref_by", "round_launches", "drain_plain_walk",
+        "pod_affinity", "first_asked")
 
 
 def run_case(case, opts=None, probe=None):
     """The record of one case on whatever library KBG_LIB_PATH names."""
     import query_update_cases as qc
     import query_update_session as qs
-    fx0, rounds_of, flags = qc.all_cases()[case][1]()
-    res = qs.check_rounds(fx0, rounds_of, opts, probe=probe, **flags)
+    cases = qc.all_cases()
+    fx0, rounds_of, flags = cases[case][1]()
+    # the ordinal of the case's first asked point: its place in its family, so that the cases of a family start the
+    # rotation of the seven calls at different calls
+    first = [c for c, (fam, _) in cases.items() if fam == cases[case][0]].index(case)
+    res = qs.check_rounds(fx0, rounds_of, opts, probe=probe, first_point=first, **flags)
     return {k: res.get(k) for k in KEEP}
 
 

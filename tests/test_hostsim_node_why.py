@@ -7,7 +7,7 @@ Kernel level: every case of tests/node_why_cases.py through the probe of that
 library against tests/node_why_ref.py, and the launches the probe refuses.
 Session level (tests/node_why_session.py): the KATs, seeds of the random,
 contended, host-port and pod-affinity generators over three action prefixes,
-two resident sessions, the refusals and the hand-derived rows of
+three resident sessions, the refusals and the hand-derived rows of
 tests/golden/kat_node_why.json. The expected rows come from the fixture and
 the oracle's output, never from the library's getters; every asked point is
 also held to kbg_task_reasons' rows of the same session, to the host path and

@@ -1,7 +1,7 @@
 """kbg_node_reasons on the device: the session checks of
 tests/node_why_session.py (expected rows from the fixture and the oracle's
 output, the transpose of kbg_task_reasons, the two paths, named nodes, the
-logs of the actions that follow, the hand-derived KAT, two resident sessions,
+logs of the actions that follow, the hand-derived KAT, three resident sessions,
 the refusals), one session whose last 64-node word is ragged past 8192 nodes,
 and one resident session queried after a preempt that left staged deltas."""
 import ctypes

@@ -1,12 +1,16 @@
-"""The four query calls on device sessions after update events:
+"""The seven query calls on device sessions after update events:
 tests/query_update_session.py's check_rounds on a subset of the hostsim cases
 (tests/test_hostsim_query_update.py) that keeps every hand-made case and at
 least four seeds per family, one case per test. A session is asked, updated
-and asked again; every point is compared with a fresh session on the replayed
-cache and with the references on the fixture after the events and the
-oracle's output. The seeded cases run twice: with the defaults and with
-KBG_HOST_TASK_WHY=1 / KBG_HOST_TASK_HEADROOM=1, so the kernels and the host
-path must agree with the same references after an update too."""
+and asked again; every point asks all seven calls of the one session, in an
+order that rotates with the point, and is compared with a fresh session on the
+replayed cache and with the references on the fixture after the events and
+the oracle's output (kbg_job_fit at limits 2 and 512, kbg_node_drain at both
+without a cordon and at 512 with one). The seeded cases run twice: with the
+defaults and with query_update_session.HOST_SWITCHES set (KBG_HOST_TASK_WHY,
+KBG_HOST_TASK_HEADROOM, KBG_HOST_JOB_FIT, KBG_HOST_NODE_WHY,
+KBG_HOST_NODE_DRAIN), so the kernels and the host path must agree with the
+same references after an update too."""
 import pytest
 
 import query_update_cases as qc
@@ -36,6 +40,9 @@ def check(case):
     print(f"{case}: {rec['rows']} rows against the fresh session, {rec['rows_ref']} against the references")
     assert rec["ref"] and rec["rows"] > 0 and rec["rows_ref"] > 0, rec
     assert min(rec["answered"]) > 0, rec
+    # (the walks' reference has no pod-affinity stage: on such fixtures kbg_node_reasons alone is held to its own)
+    for what in ("node",) if any(rec["pod_affinity"]) else ("fit", "node", "drain"):
+        assert rec["rows_ref_by"].get(what, 0) > 0, (what, rec["rows_ref_by"])
     return rec
 
 
